@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline measurement of the fake-quantization hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE pass of the hot path over one batch of synthetic input: one call of
@@ -18,7 +18,10 @@ once, when the worker has ended -- however it ended.  Round 4's driver run was l
 in an optional leg 50 s after the headline had been measured; now a dying leg costs that leg: the
 guardian records it, starts a fresh worker for the legs that are left (N = 1) and prints the line.
 
-Order of the legs (N = 1: the whole default run takes ~65 s on a fresh box; the steps/sec legs run with MIOpen's FAST find mode,
+A plain run (no --full) runs the headline leg alone: set-up, preconditioning, --warmup untimed steps, the --steps timed
+steps, the outputs of the last timed step if --dump-outputs DIR is given (dump_outputs()), and the line.  --full adds the
+extended-timing and device-to-device copy figures of the roofline and every leg after the headline, in this order
+(N = 1: the whole --full run takes ~65 s on a fresh box; the steps/sec legs run with MIOpen's FAST find mode,
 harness/legs.py miopen_env_defaults -- the default mode's first-use search for the WideResNet shapes alone took 45 s):
   headline        the timed region of the contract (+ the kernel's HIP-event time -> roofline)
   rocprof         the same kernel under rocprofv3 in child processes: --kernel-trace duration, PMC HBM traffic
@@ -59,12 +62,34 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# the default run, in order; everything after 'cifar_student' is optional (wall budget)
+# the --full run, in order (a plain run: 'headline' alone); everything after 'cifar_student' is optional (wall budget)
 LEGS = ['headline', 'rocprof', 'cpu_baseline', 'kernels', 'cifar_student',
         'cifar_graph', 'pcie_note', 'diffquant_wrn', 'imagenet_resnet18k_dp', 'nmt_lstm_dp', 'cpu_distill']
 OPTIONAL = {'cifar_graph': 4, 'pcie_note': 1, 'diffquant_wrn': 12, 'imagenet_resnet18k_dp': 4, 'nmt_lstm_dp': 9, 'cpu_distill': 12}
 #            ^ seconds a leg is expected to take on an MI355X box (profiles/r06_bench*.json legs_wall_s): it starts only if that fits the budget
 DISTILL_LEGS = ('cifar_student', 'cifar_graph', 'diffquant_wrn', 'imagenet_resnet18k_dp', 'nmt_lstm_dp')
+DUMP_SAMPLE = 1 << 22                # --dump-outputs: elements of q written (16 MiB of float32; alpha and beta are written whole)
+DUMP_SEED = 20240601
+
+
+def dump_sample_index(n, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """The sorted, distinct flat indices of q that --dump-outputs writes: a fixed seeded sample, the same in every run."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, q, sf):
+    """Write the arrays one call of the timed path returned: the seeded sample of q, and the per-bucket alpha and beta."""
+    import numpy as np
+    import torch
+    idx = dump_sample_index(q.numel())
+    arrays = {'q_sample': q.reshape(-1)[torch.from_numpy(idx).to(q.device)],
+              'alpha': sf.alpha.reshape(-1), 'beta': sf.beta.reshape(-1)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def parse_args(argv=None):
@@ -72,6 +97,12 @@ def parse_args(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='run every leg after the headline (rocprofv3, cpu_baseline, kernel rows, steps/sec legs) and the extended / '
+                         'd2d-copy figures of the roofline; without it a run times the headline alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (q: a fixed seeded sample of %d elements; alpha, beta: all '
+                         'buckets) as float32 DIR/<name>.npy (rank 0)' % DUMP_SAMPLE)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernels', action='store_true', help='skip the per-kernel roofline rows (roofline.kernels)')
     ap.add_argument('--no-distill', action='store_true', help='skip every steps/sec leg')
@@ -82,7 +113,7 @@ def parse_args(argv=None):
     ap.add_argument('--budget-s', type=float, default=None,
                     help='wall budget of the run: an OPTIONAL leg starts only if its expected duration still fits (0: no limit; default: '
                          '100 s at N = 1, 240 s at N > 1, where the steps/sec legs are what the run is for and rendezvous takes its time)')
-    ap.add_argument('--deadline-s', type=float, default=1500.0,
+    ap.add_argument('--deadline-s', type=float, default=540.0,
                     help='after this many seconds the guardian ends the worker and prints the line with what has been measured so far')
     ap.add_argument('--skip-legs', default='', help='comma-separated legs to leave out (%s)' % ', '.join(LEGS[1:]))
     ap.add_argument('--graph-at-any-n', action='store_true', help='run the hipGraph replay leg at N > 1 too (default: N = 1 only)')
@@ -97,6 +128,8 @@ def parse_args(argv=None):
 
 
 def disabled_legs(args, n_gpus):
+    if not args.full:
+        return set(LEGS) - {'headline'}      # a plain run: what the headline figure needs and nothing else
     off = set(x for x in args.skip_legs.split(',') if x)
     if args.no_cpu_baseline:
         off |= {'cpu_baseline', 'cpu_distill'}
@@ -303,10 +336,12 @@ def worker_main(args):
         for i in range(1, N_ROTATE):
             xs.append(torch.randn(N_ELEM, generator=host['gen']).to(dev))
         live = [None] * N_ROTATE
+        last = [None]
 
         def step(i):
-            q, _sf = quantization.uniformQuantization(xs[i % N_ROTATE], LEVELS, bucket_size=BUCKET)
+            q, sf = quantization.uniformQuantization(xs[i % N_ROTATE], LEVELS, bucket_size=BUCKET)
             live[i % N_ROTATE] = q            # keep the last outputs alive: rotating output buffers
+            last[0] = (q, sf)
 
         # Preconditioning (setup, untimed): from an idle GPU the first ~25 ms of back-to-back
         # launches run 10-30 % slower while the power/clock management settles
@@ -345,28 +380,41 @@ def worker_main(args):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed, event_ms_total = float(t[0]), float(t[1])
 
-        # the same measurement over >= 200 launches whatever --steps says (the driver's --steps 20 region is 1.8 ms)
-        ext_n = max(200, args.steps)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for i in range(ext_n):
-            step(i)
-        e1.record()
-        torch.cuda.synchronize()
-        ext_us = e0.elapsed_time(e1) * 1e3 / ext_n
+        # what the last timed step returned (input xs[(steps - 1) % N_ROTATE], the same in every run with these arguments)
+        if args.dump_outputs and rank == 0 and args.steps > 0:
+            dump_outputs(args.dump_outputs, *last[0])
+        last[0] = None
 
-        # reference point on this very GPU: torch's own device-to-device copy of the same 256 MiB tensors
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for i in range(3):
-            live[i % N_ROTATE].copy_(xs[i % N_ROTATE])
-        torch.cuda.synchronize()
-        c0.record()
-        for i in range(20):
-            live[i % N_ROTATE].copy_(xs[i % N_ROTATE])
-        c1.record()
-        torch.cuda.synchronize()
-        copy_gbps = bl.ALGO_BYTES_PER_ELEM * N_ELEM * 20 / (c0.elapsed_time(c1) * 1e-3) / 1e9
+        extended = {}
+        if args.full:
+            # the same measurement over >= 200 launches whatever --steps says (a --steps 20 region is 1.8 ms)
+            ext_n = max(200, args.steps)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for i in range(ext_n):
+                step(i)
+            e1.record()
+            torch.cuda.synchronize()
+            ext_us = e0.elapsed_time(e1) * 1e3 / ext_n
+
+            # reference point on this very GPU: torch's own device-to-device copy of the same 256 MiB tensors
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for i in range(3):
+                live[i % N_ROTATE].copy_(xs[i % N_ROTATE])
+            torch.cuda.synchronize()
+            c0.record()
+            for i in range(20):
+                live[i % N_ROTATE].copy_(xs[i % N_ROTATE])
+            c1.record()
+            torch.cuda.synchronize()
+            copy_gbps = bl.ALGO_BYTES_PER_ELEM * N_ELEM * 20 / (c0.elapsed_time(c1) * 1e-3) / 1e9
+            extended = {
+                'extended': {'launches': ext_n, 'avg_launch_us': round(ext_us, 3),
+                             'frac': round(bl.ALGO_BYTES_PER_ELEM * N_ELEM / (ext_us * 1e-6) / 1e9 / bl.HBM_PEAK_GBPS, 4)},
+                'extended_avg_launch_us': round(ext_us, 3),
+                'torch_d2d_copy_GBps': round(copy_gbps, 1),      # torch's own copy of the same bytes, same box (a hand-written NT copy reaches 6.3-6.5 TB/s: docs/history/profiles/r01_kbench.txt)
+            }
 
         # the GPU result the cpu_baseline leg checks (same tensor, seed 0 on rank 0)
         if rank == 0 and n_gpus == 1 and want('cpu_baseline'):
@@ -388,13 +436,10 @@ def worker_main(args):
             'traffic_source': 'profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on a '
                               'builder box (committed file, NOT measured in this run)',
             'traffic_committed': int(round(committed)) if committed else None,
-            'extended': {'launches': ext_n, 'avg_launch_us': round(ext_us, 3),
-                         'frac': round(bytes_per_launch / (ext_us * 1e-6) / 1e9 / bl.HBM_PEAK_GBPS, 4)},
-            'extended_avg_launch_us': round(ext_us, 3),
             'avg_launch_us': round(kernel_us, 3), 'algorithmic_bytes_per_launch': bytes_per_launch,
             'timing': 'HIP events on the launch stream around the %d timed launches (includes inter-launch gaps)' % args.steps,
-            'torch_d2d_copy_GBps': round(copy_gbps, 1),      # torch's own copy of the same bytes, same box (a hand-written NT copy reaches 6.3-6.5 TB/s: docs/history/profiles/r01_kbench.txt)
         }
+        roofline.update(extended)
         line.update({
             'value': round(bytes_per_launch * args.steps * n_gpus / elapsed / 1e9, 2),
             'ms_per_step': round(elapsed * 1e3 / args.steps, 5),

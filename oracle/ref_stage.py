@@ -22,7 +22,8 @@ SURVEY.md section 4) becomes `loss.item()`, and `optimizer.zero_grad()` in optim
 (conv_forward_model.py:519), after which the loop writes `points.grad.data`, becomes
 `optimizer.zero_grad(set_to_none=False)` (torch >= 2.0 drops the gradients there by default).  Nothing else is
 touched and no source is written anywhere in the repository.  load_loop(pkg) imports that loop with `import quantization`
-resolving to `pkg` -- this repository's package or the staged reference package.
+resolving to `pkg` -- this repository's package or the staged reference package.  The reference's model_manager.py
+is compiled into the same directory (tests/test_checkpoints_reference.py).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may call load() / load_loop(); the
 product (quantized_distillation_amd/, quantization/, harness/) never does.
@@ -106,6 +107,28 @@ def stage_loop(ref_root=REF_ROOT, force=False):
 
 def loop_is_staged():
     return all(os.path.exists(os.path.join(LOOP_DIR, rel + 'c')) for rel, _ in LOOP_FILES)
+
+
+# the reference's ModelManager (tests/test_checkpoints_reference.py opens our run stores with it); it imports
+# helpers/functions.py, which stage_loop() compiles into the same directory
+MANAGER_FILE = 'model_manager.py'
+
+
+def stage_model_manager(ref_root=REF_ROOT, force=False):
+    """Compile the reference's model_manager.py into oracle/_ref/loop/ (next to the staged helpers package)."""
+    src = os.path.join(ref_root, MANAGER_FILE)
+    out = os.path.join(LOOP_DIR, MANAGER_FILE + 'c')
+    if not os.path.exists(src):
+        return LOOP_DIR if model_manager_is_staged() else None
+    if stage_loop(ref_root, force) is None:
+        return None
+    if force or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
+        py_compile.compile(src, cfile=out, dfile='reference/' + MANAGER_FILE, doraise=True)
+    return LOOP_DIR
+
+
+def model_manager_is_staged():
+    return loop_is_staged() and os.path.exists(os.path.join(LOOP_DIR, MANAGER_FILE + 'c'))
 
 
 def load_loop(quantization_pkg):

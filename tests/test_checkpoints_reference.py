@@ -1,9 +1,10 @@
 """runs written by harness/checkpoints.py are opened with the REFERENCE's own
 ModelManager (model_manager.py) -- load(), load_metadata(name, run), load_model_state_dict(name),
 get_num_training_runs -- and the metadata is compared with what the reference's own save_metadata
-writes for the same dictionaries.  Runs in a subprocess with /root/reference on the path (the
-reference's `helpers.functions` imports the reference's `quantization`, which must not mix with
-this repository's package of the same name).  Skipped where /root/reference is absent (GPU box)."""
+writes for the same dictionaries.  The reference's files come from the bytecode that build() stages under
+oracle/_ref/ (oracle/ref_stage.py: model_manager, helpers.functions and the `quantization` package they import).  Runs in
+a subprocess with the staged directories on the path (the reference's `helpers.functions` imports the reference's
+`quantization`, which must not mix with this repository's package of the same name)."""
 import os
 import pickle
 import subprocess
@@ -13,15 +14,16 @@ import pytest
 import torch
 
 from harness import checkpoints, models
+from oracle import ref_stage
 
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, 'model_manager.py')),
-                                reason='the reference checkout is not present')
+pytestmark = pytest.mark.skipif(not (ref_stage.model_manager_is_staged() and ref_stage.is_staged()),
+                                reason='the reference model manager is not staged under oracle/_ref')
 
 READER = r'''
 import pickle, sys, torch
-sys.path.insert(0, %(ref)r)
+sys.path[:0] = [%(loop)r, %(stage)r]
 import model_manager
+assert model_manager.__file__.startswith(%(loop)r), model_manager.__file__
 mm = model_manager.ModelManager(%(manager)r, verbose=False)            # create_new_model_manager=False -> load()
 out = {'name': mm.name, 'models': mm.list_models(), 'runs': mm.get_num_training_runs('student'),
        'base': mm.get_model_base_path('student'),
@@ -59,7 +61,7 @@ def test_reference_model_manager_reads_our_runs(tmp_path):
     store.append_run('student', net.state_dict(), args_with_fn, info2)
     with open(tmp_path / 'raw.pkl', 'wb') as f:
         pickle.dump((raw_args, info2), f)
-    script = READER % dict(ref=REF, manager=str(tmp_path / 'manager'), raw=str(tmp_path / 'raw.pkl'),
+    script = READER % dict(loop=ref_stage.LOOP_DIR, stage=ref_stage.STAGE_DIR, manager=str(tmp_path / 'manager'), raw=str(tmp_path / 'raw.pkl'),
                            refmeta=str(tmp_path / 'ref_meta'), other=str(tmp_path / 'other'), out=str(tmp_path / 'out.pkl'))
     env = {k: v for k, v in os.environ.items() if k != 'PYTHONPATH'}
     p = subprocess.run([sys.executable, '-c', script], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE,

@@ -219,11 +219,14 @@ def test_bench_legs_and_budget_table_are_consistent():
     assert bench.LEGS.index('cpu_baseline') < bench.LEGS.index('kernels') < bench.LEGS.index('cifar_student')
     first_optional = min(bench.LEGS.index(x) for x in bench.OPTIONAL)
     assert first_optional > bench.LEGS.index('cifar_student')       # nothing optional before the legs the metric names
-    args = bench.parse_args(['--gpus', '8'])
+    args = bench.parse_args(['--gpus', '8', '--full'])
     off = bench.disabled_legs(args, 8)
     assert {'cifar_graph', 'rocprof', 'cpu_baseline', 'pcie_note', 'cpu_distill'} <= off       # N > 1: no capture next to live collectives
-    assert 'cifar_graph' not in bench.disabled_legs(bench.parse_args(['--gpus', '8', '--graph-at-any-n']), 8)
-    assert bench.disabled_legs(bench.parse_args([]), 1) == set()
+    assert 'cifar_graph' not in bench.disabled_legs(bench.parse_args(['--gpus', '8', '--full', '--graph-at-any-n']), 8)
+    assert bench.disabled_legs(bench.parse_args(['--full']), 1) == set()
+    # a plain run times the headline and nothing else, whatever the other options say
+    for argv in ([], ['--graph-at-any-n'], ['--gpus', '8']):
+        assert set(bench.LEGS) - bench.disabled_legs(bench.parse_args(argv), 1) == {'headline'}
 
 
 def test_a_signal_handler_installed_outside_python_does_not_break_the_guardian(tmp_path):

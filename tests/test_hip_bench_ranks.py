@@ -32,15 +32,56 @@ def the_line(stdout):
     return d
 
 
+def test_a_plain_run_times_the_headline_alone_and_dumps_the_last_steps_outputs(tmp_path):
+    """`python3 bench.py --gpus 1 --steps K --warmup W` runs the headline leg and nothing else: K timed steps, the contract
+    fields in the line.  --dump-outputs DIR writes what the last timed step returned, and that is the path's bit-exact result
+    on the run's seeded input (checked against the numpy oracle)."""
+    import numpy as np
+    import torch
+    import bench
+    from harness import bench_legs as bl
+    from oracle import oracle_np as onp
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    path, out = detail_path(), str(tmp_path / 'outputs')
+    steps = 6
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '2',
+                        '--dump-outputs', out, '--detail', path], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                       timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = the_line(p.stdout)
+    assert d['metric'] == 'quantize_dequantize_GBps_64M_fp32_4bit' and d['unit'] == 'GB/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f32' and d['steps'] == steps and d['warmup'] == 2 and d['n_gpus'] == 1
+    assert abs(d['value'] - 8 * d['config']['n_elements_per_gpu'] / (d['ms_per_step'] * 1e-3) / 1e9) <= 2e-3 * d['value']
+    full = json.load(open(path))
+    assert list(full['legs_wall_s']) == ['headline'], full['legs_wall_s']
+    assert full['cpu_baseline'] is None and full['distill'] is None and 'steps_per_sec' not in d
+    assert 'kernels' not in full['roofline'] and 'extended' not in full['roofline'] and 'rocprof_kernel' not in full['roofline']
+    got = {n: np.load(os.path.join(out, n + '.npy')) for n in ('q_sample', 'alpha', 'beta')}
+    assert sorted(os.listdir(out)) == ['alpha.npy', 'beta.npy', 'q_sample.npy']
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    # the last timed step quantized xs[(steps - 1) % N_ROTATE]: that many randn(N_ELEM) draws of rank 0's generator (seed 0)
+    g = torch.Generator().manual_seed(0)
+    for _ in range((steps - 1) % bl.N_ROTATE + 1):
+        x = torch.randn(bl.N_ELEM, generator=g)
+    want = onp.uniform_quantize(x.numpy(), bl.LEVELS, bl.BUCKET)
+    idx = bench.dump_sample_index(bl.N_ELEM)
+    assert len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got['q_sample'], want['q'].reshape(-1)[idx])
+    assert np.array_equal(got['alpha'], want['alpha'].reshape(-1)) and np.array_equal(got['beta'], want['beta'].reshape(-1))
+
+
 def test_the_driver_command_prints_one_line_of_at_most_4096_bytes_with_roofline_and_cpu_baseline():
-    """`python3 bench.py --gpus 1 --steps 20 --warmup 5` (+ --quick: short steps/sec legs): the line parses from the last 6000
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` (+ --quick: short steps/sec legs): the line parses from the last 6000
     bytes of stdout and carries the contract fields, `roofline` with measured traffic and `cpu_baseline`; everything else is in
     the detail file."""
     env = dict(os.environ)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     path = detail_path()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--quick', '--detail', path],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--full', '--quick',
+                        '--detail', path],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     d = the_line(p.stdout)
@@ -69,8 +110,9 @@ def test_two_ranks_quick_run_end_to_end():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     path = detail_path()
-    cmd = launch.launcher_command(os.path.join(ROOT, 'bench.py'), 2, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--quick', '--no-cpu-baseline',
-                                                                       '--no-pmc', '--no-kernels', '--precondition-s', '0.05', '--detail', path,
+    cmd = launch.launcher_command(os.path.join(ROOT, 'bench.py'), 2, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--quick',
+                                                                       '--no-cpu-baseline', '--no-pmc', '--no-kernels', '--precondition-s', '0.05',
+                                                                       '--detail', path,
                                                                        '--skip-legs', 'diffquant_wrn,nmt_lstm_dp'])     # (all four legs: tools/gpu_session.sh ranks2)
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -110,8 +152,9 @@ def test_a_failed_preflight_collective_still_yields_the_line():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     path = detail_path()
-    cmd = launch.launcher_command(os.path.join(ROOT, 'bench.py'), 2, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--quick', '--no-cpu-baseline',
-                                                                       '--no-pmc', '--no-kernels', '--precondition-s', '0.05', '--detail', path])
+    cmd = launch.launcher_command(os.path.join(ROOT, 'bench.py'), 2, ['--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--quick',
+                                                                       '--no-cpu-baseline', '--no-pmc', '--no-kernels', '--precondition-s', '0.05',
+                                                                       '--detail', path])
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = the_line(p.stdout)
@@ -130,7 +173,7 @@ def test_a_leg_that_aborts_the_worker_costs_that_leg_only():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     path = detail_path()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--quick', '--no-pmc',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--full', '--quick', '--no-pmc',
                         '--precondition-s', '0.05', '--skip-legs', 'diffquant_wrn,nmt_lstm_dp,imagenet_resnet18k_dp,kernels',
                         '--deadline-s', '300', '--detail', path],          # (the guardian's own wall limit: a hang costs minutes, not the suite)
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)

@@ -5,7 +5,8 @@
 #   tests      the whole GPU suite (records the achieved reduction errors in gpurun_out/reduction_error.jsonl)
 #   driver     the driver's exact command (python3 bench.py --gpus 1 --steps 20 --warmup 5): stdout line + bench_detail.json,
 #              numbered by DRIVER_TAG; checks that the line parses from the last 6000 bytes of stdout
-#   bench      bench.py with its default flags
+#   bench      bench.py --full with its default steps (every leg)
+#   (bench, torchrun and ranks2 write under $OUT, default build/session/)
 #   prof       rocprofv3 --kernel-trace --stats of the bench command (its measuring process, `bench.py --worker`) + the two PMC passes
 #   kernels    tools/bench_kernels.py (every kernel of the path, steady state);  kprof: the same under rocprofv3 --kernel-trace --stats
 #   torchrun   bench.py under torch.distributed.run with one rank;  ranks2: two ranks on this one GPU through gloo
@@ -20,6 +21,8 @@
 set +e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $R/gpurun_out
+OUT=${OUT:-$R/build/session}
+mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R
 for step in "$@"; do
@@ -43,11 +46,11 @@ print('steps/s', d.get('steps_per_sec'))
 print('legs', d.get('legs_wall_s'), '| process', d.get('bench_process'))
 PYEOF
              ;;
-    bench)   timeout 1500 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$? bytes=$(wc -c < gpurun_out/bench.json)"; cp bench_detail.json gpurun_out/bench_detail.json; cat gpurun_out/bench.json ;;
+    bench)   timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? bytes=$(wc -c < $OUT/bench.json)"; cp bench_detail.json $OUT/bench_detail.json; cat $OUT/bench.json ;;
     torchrun) # the way the driver starts N > 1, with one rank: env rendezvous, RCCL group from the launcher's environment
-             timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --detail gpurun_out/bench_detail_torchrun.json > gpurun_out/bench_torchrun.json 2> gpurun_out/bench_torchrun.err; echo "torchrun rc=$? bytes=$(wc -c < gpurun_out/bench_torchrun.json)"; tail -1 gpurun_out/bench_torchrun.json | cut -c1-400 ;;
+             timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-pmc --detail $OUT/bench_detail_torchrun.json > $OUT/bench_torchrun.json 2> $OUT/bench_torchrun.err; echo "torchrun rc=$? bytes=$(wc -c < $OUT/bench_torchrun.json)"; tail -1 $OUT/bench_torchrun.json | cut -c1-400 ;;
     ranks2)  # the whole multi-rank flow on this one GPU: two ranks on device 0, collectives through gloo (bench.py QD_BENCH_BACKEND)
-             QD_BENCH_BACKEND=gloo QD_BENCH_ONE_GPU=1 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --steps 20 --warmup 5 --no-kernels --detail gpurun_out/bench_detail_two_ranks_one_gpu.json > gpurun_out/bench_two_ranks_one_gpu.json 2> gpurun_out/bench_two_ranks_one_gpu.err; echo "ranks2 rc=$? bytes=$(wc -c < gpurun_out/bench_two_ranks_one_gpu.json)"; tail -1 gpurun_out/bench_two_ranks_one_gpu.json ;;
+             QD_BENCH_BACKEND=gloo QD_BENCH_ONE_GPU=1 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --steps 20 --warmup 5 --full --no-kernels --detail $OUT/bench_detail_two_ranks_one_gpu.json > $OUT/bench_two_ranks_one_gpu.json 2> $OUT/bench_two_ranks_one_gpu.err; echo "ranks2 rc=$? bytes=$(wc -c < $OUT/bench_two_ranks_one_gpu.json)"; tail -1 $OUT/bench_two_ranks_one_gpu.json ;;
     kprof)   # the kernel rows under rocprofv3: the per-kernel average durations next to the HIP-event figures
              rm -rf gpurun_out/kprof_stats
              (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/kprof_stats -o kernels -- python $R/tools/bench_kernels.py 26 --no-sweeps > $R/gpurun_out/kernels_under_rocprof.txt 2> $R/gpurun_out/kprof.err); echo "kprof rc=$?"
