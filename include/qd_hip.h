@@ -56,7 +56,8 @@ extern "C" {
  * History: 1 = rounds 1-3; 2 = qd_nearest_point_f32 accepts q == NULL (indices only), qd_uniform_f32 accepts q == NULL with
  * level_idx (levels only), qd_selftest_div_invariant, qd_digitize_histogram_f32 / qd_histogram_i64 / qd_level_histogram_f32
  * added, 4-byte data alignment; 3 = qd_scale_digitize_histogram_f32 added, QdDiffQuantDesc.first_row (partial rows of
- * qd_multi_point_grad_f32 per tensor size instead of 4 B + 1 for every tensor).
+ * qd_multi_point_grad_f32 per tensor size instead of 4 B + 1 for every tensor); qd_huffman_encode / qd_huffman_decode_f32
+ * were added later without a bump (new symbols only, nothing existing changed meaning).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -282,6 +283,53 @@ int qd_histogram_i64(const int64_t* idx, int64_t n, int k, uint64_t* hist, void*
  * otherwise, and the caller takes the two-call form.  edges, hist, workspace as for qd_digitize_histogram_f32. */
 int qd_scale_digitize_histogram_f32(const float* q, int64_t n, int64_t bucket, const double* edges, int m, uint64_t* hist,
                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Huffman-coded model checkpoints (quantized_distillation_amd/compressed.py).  The reference only
+ * ACCOUNTS for this form: helpers/functions.py:226-262 charges the Huffman mean code length of
+ * quantization/help_functions.py:157-232 per quantized weight plus 8 B (alpha, beta) per bucket, and saves the student as a
+ * full fp32 state_dict (cifar10_test.py:265-270).  These two entry points write and read that form.
+ * Symbols (one uint8 per element: the level index of qd_uniform_f32 or the point index of qd_nearest_point_f32) are coded
+ * with ONE canonical code for the whole model, codewords of at most 32 bits, most significant bit first inside 32-bit words.
+ * Every tensor is cut into chunks of QD_HUF_CHUNK symbols (its last chunk may be shorter); chunk c starts on word
+ * chunk_words[c] of the bitstream and never shares a word with another chunk.
+ * QdHufTensor: one entry per quantized tensor, in file order (a DEVICE array for libqd_hip.so, host for libqd_host.so).
+ * QdHufCode: the canonical code, built from the code lengths (compressed.py: canonical_code). */
+#define QD_HUF_CHUNK 1024
+typedef struct QdHufTensor {
+    const uint8_t* sym;      /* encode: the tensor's n symbols                                     */
+    float* y;                /* decode: the tensor's n fp32 outputs                                */
+    int64_t n;               /* elements                                                          */
+    int64_t first_chunk;     /* sum of ceil(n_j / QD_HUF_CHUNK) over the tensors before this one    */
+    int64_t first_bucket;    /* decode: index of the tensor's first (alpha, beta) in alpha / beta  */
+    int64_t first_point;     /* decode, non-uniform: index of the tensor's first point in points   */
+    int64_t bucket;          /* decode: bucket size, 0 = one (alpha, beta) for the whole tensor     */
+    int32_t levels;          /* decode: s (uniform) or k (non-uniform); a symbol >= levels decodes to NaN */
+    int32_t nonuniform;      /* decode: 0 = (idx/(s-1))*alpha + beta, 1 = points[idx]*alpha + beta */
+} QdHufTensor;
+typedef struct QdHufCode {
+    uint32_t code[256];      /* codeword of each symbol, right-aligned                            */
+    uint32_t base[33];       /* first codeword of each length                                     */
+    uint32_t count[33];      /* number of codewords of each length                                */
+    uint32_t first[33];      /* position in sorted[] of the first symbol of each length           */
+    uint8_t len[256];        /* code length of each symbol, 0 = not in the code                   */
+    uint8_t sorted[256];     /* symbols in canonical order (length, then symbol)                  */
+    int32_t single;          /* the only symbol of a one-symbol code (0 bits per symbol), else -1  */
+    int32_t max_len;         /* longest codeword, <= 32                                           */
+} QdHufCode;
+/* qd_huffman_encode: the chunked bitstream of every tensor of `table` in three launches, however many tensors there are
+ *   (per-chunk word counts, one exclusive scan over the chunks, the write; each chunk is assembled in LDS and stored as whole
+ *   words).  chunk_words: [nchunks + 1] outputs, chunk_words[nchunks] = total words.  words: [max_words] output; a chunk that
+ *   would end beyond max_words is not written (callers size it from the histogram: sum(count*len)/32 + nchunks words).
+ *   Lengths: help_functions.py:157-172 (huffman_encode) over the histogram of :213-231, canonically numbered.
+ * qd_huffman_decode_f32: ONE launch decodes every tensor of `table` and dequantizes in registers, writing fp32 straight to
+ *   each tensor's y: uniform (idx/(s-1))*alpha + beta, as qd_unpack_uniform_f32 (= uniformQuantization, quant_functions.py:
+ *   155-194); non-uniform points[idx]*alpha + beta, as K4's rescale (quant_functions.py:278-286).  nwords bounds every read of
+ *   the bitstream.  Both: 4-byte aligned arrays; nchunks >= 1, ntensors >= 1. */
+int qd_huffman_encode(const QdHufTensor* table, int ntensors, int64_t nchunks, const QdHufCode* code, uint32_t* chunk_words,
+                      uint32_t* words, int64_t max_words, void* stream);
+int qd_huffman_decode_f32(const uint32_t* words, int64_t nwords, const uint32_t* chunk_words, const QdHufTensor* table,
+                          int ntensors, int64_t nchunks, const QdHufCode* code, const float* alpha, const float* beta,
+                          const float* points, void* stream);
 
 /* ---- order statistics for initialize_quantization_points (quantization/help_functions.py:140-154: the reference
  * copies the scaled tensor to the host and calls np.percentile(a, linspace(0, 100, k)), which needs the two

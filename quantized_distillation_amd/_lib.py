@@ -49,6 +49,20 @@ class QdDiffQuantDesc(ctypes.Structure):
                 ('first_tile', ctypes.c_int64), ('first_block', ctypes.c_int64), ('first_row', ctypes.c_int64)]
 
 
+class QdHufTensor(ctypes.Structure):
+    """Mirror of `struct QdHufTensor` in include/qd_hip.h."""
+    _fields_ = [('sym', ctypes.c_void_p), ('y', ctypes.c_void_p), ('n', ctypes.c_int64), ('first_chunk', ctypes.c_int64),
+                ('first_bucket', ctypes.c_int64), ('first_point', ctypes.c_int64), ('bucket', ctypes.c_int64),
+                ('levels', ctypes.c_int32), ('nonuniform', ctypes.c_int32)]
+
+
+class QdHufCode(ctypes.Structure):
+    """Mirror of `struct QdHufCode` in include/qd_hip.h."""
+    _fields_ = [('code', ctypes.c_uint32 * 256), ('base', ctypes.c_uint32 * 33), ('count', ctypes.c_uint32 * 33),
+                ('first', ctypes.c_uint32 * 33), ('len', ctypes.c_uint8 * 256), ('sorted', ctypes.c_uint8 * 256),
+                ('single', ctypes.c_int32), ('max_len', ctypes.c_int32)]
+
+
 # symbol -> (restype, argtypes); every symbol declared in include/qd_hip.h must be listed here
 # (tests/test_abi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -94,6 +108,8 @@ SIGNATURES = {
     'qd_order_stats_workspace_bytes': (ctypes.c_size_t, [c_int]),
     'qd_order_stats_f32': (c_int, [c_p, i64, c_p, c_int, c_p, c_p, ctypes.c_size_t, c_p]),
     'qd_selftest_div_invariant': (c_int, [u64, i64, c_int, c_p, c_p]),
+    'qd_huffman_encode': (c_int, [c_p, c_int, i64, c_p, c_p, c_p, i64, c_p]),
+    'qd_huffman_decode_f32': (c_int, [c_p, i64, c_p, c_p, c_int, i64, c_p, c_f, c_f, c_f, c_p]),
 }
 
 
@@ -126,11 +142,12 @@ def load():
     return _lib
 
 
-# the entry points libqd_host.so implements (the per-call functions; multi-tensor, codec, order statistics and the
-# 'absmax' / 'absnorm' scalings exist for device tensors only)
+# the entry points libqd_host.so implements (the per-call functions and the Huffman checkpoint codec; multi-tensor, packed
+# codec, order statistics and the 'absmax' / 'absnorm' scalings exist for device tensors only)
 HOST_SYMBOLS = ('qd_abi_version', 'qd_target_arch', 'qd_error_string', 'qd_workspace_bytes', 'qd_num_buckets', 'qd_padded_length',
                 'qd_mean_f32', 'qd_uniform_f32', 'qd_scale_down_f32', 'qd_inv_scale_f32', 'qd_bucket_argminmax_f32',
-                'qd_nearest_point_f32', 'qd_point_grad_f32', 'qd_ste_bucket_backward_f32', 'qd_clamp_f32', 'qd_truncated_ste_f32')
+                'qd_nearest_point_f32', 'qd_point_grad_f32', 'qd_ste_bucket_backward_f32', 'qd_clamp_f32', 'qd_truncated_ste_f32',
+                'qd_huffman_encode', 'qd_huffman_decode_f32')
 _host = None
 
 

@@ -19,8 +19,9 @@
 // -ffp-contract=off -fno-fast-math (quantized_distillation_amd/build.py): no fused multiply-add, no reassociation.
 //
 // Entry points present: qd_mean_f32, qd_uniform_f32, qd_scale_down_f32, qd_inv_scale_f32, qd_bucket_argminmax_f32,
-// qd_nearest_point_f32, qd_point_grad_f32, qd_ste_bucket_backward_f32, qd_clamp_f32, qd_truncated_ste_f32 and the host
-// helpers.  The multi-tensor, codec, order-statistics and 'absmax' / 'absnorm' entry points exist for device tensors only.
+// qd_nearest_point_f32, qd_point_grad_f32, qd_ste_bucket_backward_f32, qd_clamp_f32, qd_truncated_ste_f32, the Huffman
+// checkpoint codec (qd_huffman_encode, qd_huffman_decode_f32) and the host helpers.  The multi-tensor, packed-codec,
+// order-statistics and 'absmax' / 'absnorm' entry points exist for device tensors only.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -610,6 +611,138 @@ int qd_truncated_ste_f32(const float* w, float* grad, int64_t n, float limit, vo
 #pragma omp parallel for schedule(static) if (n >= kParallelMin)
     for (int64_t i = 0; i < n; ++i)
         if (std::fabs(w[i]) > limit) grad[i] = 0.0f;
+    return 0;
+}
+
+// Huffman-coded checkpoints (csrc/qd_huffman.hip, include/qd_hip.h): the same chunked canonical-code bitstream, word for
+// word, and the same dequantization -- a file written by either library is byte-identical and reads back bit-identically
+// in either.
+static int huf_find_tensor(const QdHufTensor* table, int nt, int64_t c) {
+    int lo = 0, hi = nt - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_chunk <= c) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+static int huf_chunk_span(const QdHufTensor& T, int64_t c, int64_t& e0) {
+    e0 = (c - T.first_chunk) * QD_HUF_CHUNK;
+    const int64_t left = T.n - e0;
+    return left < QD_HUF_CHUNK ? (left > 0 ? (int)left : 0) : QD_HUF_CHUNK;
+}
+
+int qd_huffman_encode(const QdHufTensor* table, int ntensors, int64_t nchunks, const QdHufCode* code, uint32_t* chunk_words,
+                      uint32_t* words, int64_t max_words, void*) {
+    if (!table || !code || ntensors < 1 || nchunks < 1 || nchunks > 0x7fffffffLL || !chunk_words || !words || max_words < 1)
+        return QD_ERR_INVALID_ARGUMENT;
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const QdHufTensor& T = table[huf_find_tensor(table, ntensors, c)];
+        int64_t e0;
+        const int cnt = huf_chunk_span(T, c, e0);
+        uint32_t bits = 0;
+        for (int i = 0; i < cnt; ++i) bits += code->len[T.sym[e0 + i]];
+        chunk_words[c] = (bits + 31u) >> 5;
+    }
+    uint32_t run = 0;
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const uint32_t v = chunk_words[c];
+        chunk_words[c] = run;
+        run += v;
+    }
+    chunk_words[nchunks] = run;
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const QdHufTensor& T = table[huf_find_tensor(table, ntensors, c)];
+        int64_t e0;
+        const int cnt = huf_chunk_span(T, c, e0);
+        const uint32_t w0 = chunk_words[c], nw = chunk_words[c + 1] - w0;
+        if (nw > (uint32_t)QD_HUF_CHUNK || (int64_t)w0 + (int64_t)nw > max_words) continue;
+        uint32_t* out = words + w0;
+        for (uint32_t i = 0; i < nw; ++i) out[i] = 0u;
+        uint32_t p = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const uint32_t s = T.sym[e0 + i], L = code->len[s], cd = code->code[s];
+            if (!L) continue;
+            const uint32_t w = p >> 5, off = p & 31u;
+            if (off + L <= 32u) {
+                out[w] |= cd << (32u - off - L);
+            } else {
+                out[w] |= cd >> (off + L - 32u);
+                out[w + 1] |= cd << (64u - off - L);
+            }
+            p += L;
+        }
+    }
+    return 0;
+}
+
+int qd_huffman_decode_f32(const uint32_t* words, int64_t nwords, const uint32_t* chunk_words, const QdHufTensor* table,
+                          int ntensors, int64_t nchunks, const QdHufCode* code, const float* alpha, const float* beta,
+                          const float* points, void*) {
+    if (!table || !code || ntensors < 1 || nchunks < 1 || nchunks > 0x7fffffffLL || !chunk_words || !alpha || !beta ||
+        nwords < 0 || (nwords > 0 && !words))
+        return QD_ERR_INVALID_ARGUMENT;
+    const int max_len = code->max_len, single = code->single;
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const QdHufTensor& T = table[huf_find_tensor(table, ntensors, c)];
+        int64_t e0;
+        const int cnt = huf_chunk_span(T, c, e0);
+        if (cnt <= 0) continue;
+        const int64_t bucket = T.bucket;
+        int64_t bidx = 0, rem = 0;
+        if (bucket > 0) { bidx = e0 / bucket; rem = e0 - bidx * bucket; }
+        float a = alpha[T.first_bucket + bidx], b = beta[T.first_bucket + bidx];
+        const float sm1 = (float)(T.levels - 1);
+        const float* pts = T.nonuniform ? points + T.first_point : nullptr;
+        float* y = T.y + e0;
+        uint32_t wp = chunk_words[c];
+        const int64_t we = chunk_words[c + 1];
+        const uint32_t wend = (uint32_t)(we < nwords ? we : nwords);
+        uint64_t buf = 0;
+        int nb = 0;
+        for (int e = 0; e < cnt; ++e) {
+            if (nb < 32) {
+                const uint32_t w = wp < wend ? words[wp] : 0u;
+                ++wp;
+                buf |= (uint64_t)w << (32 - nb);
+                nb += 32;
+            }
+            uint32_t sym = 0xffffu, L = 32;
+            if (single >= 0) {
+                sym = (uint32_t)single;
+                L = 0;
+            } else {
+                for (int l = 1; l <= max_len; ++l) {
+                    const uint32_t cc = (uint32_t)(buf >> (64 - l));
+                    if (cc - code->base[l] < code->count[l]) { sym = code->sorted[code->first[l] + cc - code->base[l]]; L = (uint32_t)l; break; }
+                }
+            }
+            buf <<= L;
+            nb -= (int)L;
+            float v;
+            if (sym >= (uint32_t)T.levels) {
+                v = std::numeric_limits<float>::quiet_NaN();
+            } else if (T.nonuniform) {
+                v = pts[sym] * a;
+                v = v + b;
+                v = v + 0.0f;
+            } else {
+                const float w = (float)sym / sm1;
+                v = w * a;
+                v = v + b;
+                v = v + 0.0f;
+            }
+            y[e] = v;
+            if (bucket > 0 && ++rem == bucket) {
+                rem = 0;
+                ++bidx;
+                if (e + 1 < cnt) { a = alpha[T.first_bucket + bidx]; b = beta[T.first_bucket + bidx]; }
+            }
+        }
+    }
     return 0;
 }
 
