@@ -20,7 +20,7 @@ import torch
 
 import quantization
 from quantized_distillation_amd import ste
-from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer
+from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer, MultiTensorSTE
 
 from . import models
 from .flat import FlatLayout, GradSynchronizer, broadcast_from_rank0
@@ -99,6 +99,8 @@ class DistillTrainer(object):
             qi = [i for i in range(n) if self.quantized[i]]
             self.mt = MultiTensorQuantizer([self.masters[i] for i in qi], self.s, bucket_size,
                                            outputs=[shadows[i] for i in qi])
+            if style == 'complicated':                           # K7 over all quantized masters, in place on the flat gradient
+                self.mt_ste = MultiTensorSTE([self.masters[i] for i in qi], [grads[i] for i in qi], self.s, bucket_size)
         else:
             for i, p in enumerate(params):
                 p.data = self.masters[i]
@@ -150,6 +152,8 @@ class DistillTrainer(object):
         if self.style == 'truncated':                            # ref: :263-264 p.grad[p.data.abs() > 1] = 0
             for a, b in self.qranges:
                 ste.truncated_ste_(self.flat_grad[a:b], self.flat_master[a:b], 1.0)
+        elif self.mode == 'multi':                               # 'complicated', one launch for the whole model
+            self.mt_ste.backward(check_pointers=False)
         else:                                                    # 'complicated', ref: :265-266 -> quant_functions.py:319-406
             grads = self.layout.views(self.flat_grad)
             for i in range(len(self.params)):

@@ -57,7 +57,8 @@ extern "C" {
  * level_idx (levels only), qd_selftest_div_invariant, qd_digitize_histogram_f32 / qd_histogram_i64 / qd_level_histogram_f32
  * added, 4-byte data alignment; 3 = qd_scale_digitize_histogram_f32 added, QdDiffQuantDesc.first_row (partial rows of
  * qd_multi_point_grad_f32 per tensor size instead of 4 B + 1 for every tensor); qd_huffman_encode / qd_huffman_decode_f32
- * were added later without a bump (new symbols only, nothing existing changed meaning).
+ * and qd_multi_ste_plan / qd_multi_ste_backward_f32 were added later without a bump (new symbols only, nothing existing
+ * changed meaning).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -185,6 +186,28 @@ int qd_multi_uniform_f32(const QdTensorDesc* table, int ntensors, int64_t total_
 int64_t qd_multi_global_plan(QdTensorDesc* host_table, int ntensors);
 int qd_multi_uniform_global_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int levels,
                                 float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Multi-tensor K7: the 'complicated' straight-through backward of every quantized parameter of a model in ONE launch (the
+ * per-step loop `quantizeFunctions[idx].backward(p.grad.data)`, cnn_models/conv_forward_model.py:253-266).  `table` is a
+ * DEVICE array of descriptors; each tensor is bucketed independently with the same bucket / levels / tie_mode and its result
+ * is bit-identical to qd_ste_bucket_backward_f32 on the same pointers: every bucket takes the path the per-tensor call
+ * would give it and is summed in that order.  No workspace, no allocation, no synchronisation.  bucket must be > 0. */
+typedef struct QdSteDesc {
+    const float* x;      /* full-precision weights the forward quantized   */
+    const float* g;      /* dLoss/dq                                        */
+    float* out;          /* result; may alias g                             */
+    int64_t n;
+    int64_t first_tile;  /* filled by qd_multi_ste_plan                     */
+} QdSteDesc;
+/* Host helper: fills first_tile of `ntensors` HOST descriptors (x, g, out, n set: the tile rule depends on the pointers'
+ * alignment) and writes the total tile count, to be passed to qd_multi_ste_backward_f32.  A tile is one wave iteration on
+ * one tensor.  Tensors whose bucket row (min(n, bucket)) is 64 / 128 / 256 / 512 / 1024, that hold more than one bucket and
+ * whose x, g, out are 4-byte aligned own ceil((n / row) / B) register tiles of B = 4 (row <= 256) or 1 (row >= 512) full
+ * buckets, then one single-bucket tile for a ragged last bucket; every other tensor owns one tile per bucket; an empty
+ * tensor owns none.  Returns 0 or QD_ERR_INVALID_ARGUMENT. */
+int qd_multi_ste_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out);
+int qd_multi_ste_backward_f32(const QdSteDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, int levels,
+                              int tie_mode, void* stream);
 
 /* ---- 'absmax' / 'absnorm' scaling (type_scaling of ScalingFunction, quant_functions.py:109-127,144-146).
  * PARITY UNPINNED: the reference code for these two types raises on every torch version, so these

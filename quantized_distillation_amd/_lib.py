@@ -42,6 +42,12 @@ class QdTensorDesc(ctypes.Structure):
                 ('first_tile', ctypes.c_int64)]
 
 
+class QdSteDesc(ctypes.Structure):
+    """Mirror of `struct QdSteDesc` in include/qd_hip.h."""
+    _fields_ = [('x', ctypes.c_void_p), ('g', ctypes.c_void_p), ('out', ctypes.c_void_p), ('n', ctypes.c_int64),
+                ('first_tile', ctypes.c_int64)]
+
+
 class QdDiffQuantDesc(ctypes.Structure):
     """Mirror of `struct QdDiffQuantDesc` in include/qd_hip.h."""
     _fields_ = [('u', ctypes.c_void_p), ('q', ctypes.c_void_p), ('idx', ctypes.c_void_p), ('alpha', ctypes.c_void_p),
@@ -89,6 +95,8 @@ SIGNATURES = {
     'qd_multi_uniform_f32': (c_int, [c_p, c_int, i64, i64, c_int, c_p]),
     'qd_multi_global_plan': (i64, [ctypes.POINTER(QdTensorDesc), c_int]),
     'qd_multi_uniform_global_f32': (c_int, [c_p, c_int, i64, c_int, c_f, c_p, c_size, c_p]),
+    'qd_multi_ste_plan': (c_int, [ctypes.POINTER(QdSteDesc), c_int, i64, ctypes.POINTER(ctypes.c_int64)]),
+    'qd_multi_ste_backward_f32': (c_int, [c_p, c_int, i64, i64, c_int, c_int, c_p]),
     'qd_uniform_abs_f32': (c_int, [c_f, c_f, i64, i64, c_int, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_scale_down_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_inv_scale_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_f, c_f, c_p]),

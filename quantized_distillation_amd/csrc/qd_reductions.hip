@@ -662,21 +662,16 @@ __device__ __forceinline__ bool ste_tiny_numerator(float x, float bq) {     // 0
 
 // vector path: LPB lanes per bucket, V float4 per lane, the whole bucket (x, g, q) in registers, one pass.  Index ties:
 // the FIRST element (in memory order) at the top / bottom level of the quantized bucket (or the true arg of x).
+// One tile (= one wave iteration, 64 / LPB buckets) of the vector path: the body of k_ste_backward_vec and of the register
+// tiles of k_multi_ste, so that both sum a bucket in the same order.
 template <int LPB, int V>
-__global__ __launch_bounds__(256) void k_ste_backward_vec(const float* x, const float* g, float* out, int64_t nvec,
-                                                          float sm1, int tie_mode) {
-    constexpr int BPW = 64 / LPB;
+__device__ __forceinline__ void ste_vec_tile(const float* x, const float* g, float* out, int64_t nvec, int64_t t, int sub, int l,
+                                             float sm1, int tie_mode, bool use_tab, float tab) {
+    constexpr int BPW = 64 / LPB;                            // sub = lane / LPB: the bucket of the tile, l = lane % LPB
     constexpr int ROW = LPB * V * 4;
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / LPB, l = lane % LPB;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    const int64_t ntiles = (nvec + BPW - 1) / BPW;
-    const bool use_tab = sm1 <= 15.0f;                       // DPP rows are active or inactive as a whole here (qdq_tab)
-    const float tab = (float)(lane & 15) / sm1;
-    for (int64_t t = wave; t < ntiles; t += nwaves) {
+    {
         const int64_t bkt = t * BPW + sub;
-        if (bkt >= nvec) continue;
+        if (bkt >= nvec) return;
         const int64_t e0 = bkt * ROW + (int64_t)l * 4;
         f4 xv[V], gv[V], qv[V];
 #pragma unroll
@@ -768,13 +763,25 @@ __global__ __launch_bounds__(256) void k_ste_backward_vec(const float* x, const 
     }
 }
 
-// any bucket size / alignment: one wave per bucket, four passes over the (L1/L2-resident) bucket
-__global__ __launch_bounds__(256) void k_ste_backward(const float* x, const float* g, float* out, int64_t n,
-                                                      int64_t row, int64_t first, int64_t nb, float sm1, int tie_mode) {
+template <int LPB, int V>
+__global__ __launch_bounds__(256) void k_ste_backward_vec(const float* x, const float* g, float* out, int64_t nvec,
+                                                          float sm1, int tie_mode) {
+    constexpr int BPW = 64 / LPB;
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t bkt = first + wave; bkt < nb; bkt += nwaves) {
+    const int64_t ntiles = (nvec + BPW - 1) / BPW;
+    const bool use_tab = sm1 <= 15.0f;                       // DPP rows are active or inactive as a whole here (qdq_tab)
+    const float tab = (float)(lane & 15) / sm1;
+    const int sub = lane / LPB, l = lane % LPB;
+    for (int64_t t = wave; t < ntiles; t += nwaves) ste_vec_tile<LPB, V>(x, g, out, nvec, t, sub, l, sm1, tie_mode, use_tab, tab);
+}
+
+// any bucket size / alignment: one wave per bucket, four passes over the (L1/L2-resident) bucket.  The body of k_ste_backward
+// and of the generic tiles of k_multi_ste.
+__device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, float* out, int64_t n, int64_t row, int64_t bkt,
+                                                int lane, float sm1, int tie_mode) {
+    {
         const int64_t lo = bkt * row;
         const int64_t hi = lo + row < n ? lo + row : n;
         // pass 1: alpha/beta of x
@@ -832,6 +839,14 @@ __global__ __launch_bounds__(256) void k_ste_backward(const float* x, const floa
             out[i] = o;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_ste_backward(const float* x, const float* g, float* out, int64_t n,
+                                                      int64_t row, int64_t first, int64_t nb, float sm1, int tie_mode) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t bkt = first + wave; bkt < nb; bkt += nwaves) ste_wave_bucket(x, g, out, n, row, bkt, lane, sm1, tie_mode);
 }
 
 // ---- K8: 'truncated' STE ----------------------------------------------------------------------
@@ -954,6 +969,66 @@ __global__ __launch_bounds__(256) void k_multi_uniform(const QdTensorDesc* __res
             if (fdiv) body(std::true_type{}); else body(std::false_type{});
         } else {
             bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
+        }
+    }
+}
+
+// ---- multi-tensor K7: the 'complicated' STE backward of every parameter of a model in one launch ----
+// A tile = one wave iteration on one tensor.  Every tensor is cut exactly as qd_ste_bucket_backward_f32 cuts it, so that each
+// bucket is summed by the same body in the same order and the result is bit-identical to the per-tensor call:
+//   * register tiles: when the bucket row is 64 / 128 / 256 / 512 / 1024, the tensor has more than one bucket and x, g, out
+//     meet the data alignment (kDataAlign), the n / row full buckets go through ste_vec_tile<LPB, V>, 64 / LPB buckets per
+//     tile (4 up to row 256, 1 above) -- tiles 0 .. vt - 1 of the tensor, bucket t * (64 / LPB) + lane / LPB;
+//   * generic tiles: one bucket per tile through ste_wave_bucket -- the ragged last bucket after the register tiles (tile vt),
+//     or every bucket of the tensor (tile = bucket) when the register path does not apply.
+// ste_tiles() is that rule for the host plan; k_multi_ste<LPB, V> applies it with the row as a constant (a launch has ONE
+// bucket size, so at most one register instantiation; tensors shorter than a bucket are a single generic tile).
+inline int ste_lanes_per_bucket(int64_t row) {
+    return (row == 64 || row == 128 || row == 256) ? 16 : (row == 512 || row == 1024) ? 64 : 0;
+}
+inline int64_t ste_tiles(const QdSteDesc& d, int64_t bucket) {
+    if (d.n <= 0) return 0;
+    int64_t nb, row;
+    geometry(d.n, bucket, nb, row);
+    const int lpb = ste_lanes_per_bucket(row);
+    const bool aligned = (((((uintptr_t)d.x) | ((uintptr_t)d.g) | ((uintptr_t)d.out)) & kDataAlign) == 0) && nb > 1;
+    if (!lpb || !aligned) return nb;
+    const int64_t nfull = d.n / row, bpw = 64 / lpb;
+    return (nfull + bpw - 1) / bpw + (nb - nfull);
+}
+
+template <int LPB, int V>
+__global__ __launch_bounds__(256) void k_multi_ste(const QdSteDesc* __restrict__ table, int ntensors, int64_t total_tiles,
+                                                   int64_t bucket, float sm1, int tie_mode) {
+    constexpr int ROW = LPB * V * 4;                  // 0: no register path at this bucket size
+    constexpr int BPW = LPB > 0 ? 64 / LPB : 1;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: the table search below runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const bool use_tab = sm1 <= 15.0f;
+    const float tab = (float)(lane & 15) / sm1;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        int lo_t = 0, hi_t = ntensors - 1;               // last tensor with first_tile <= t (an empty tensor owns no tile)
+        while (lo_t < hi_t) {
+            const int mid = (lo_t + hi_t + 1) >> 1;
+            if (table[mid].first_tile <= t) lo_t = mid; else hi_t = mid - 1;
+        }
+        const QdSteDesc d = table[lo_t];
+        if (d.n <= 0) continue;
+        const int64_t local = t - d.first_tile;
+        const int64_t row = d.n < bucket ? d.n : bucket;
+        int64_t nfull = 0, vt = 0;
+        if (LPB > 0 && row == ROW && d.n > ROW &&
+            (((((uintptr_t)d.x) | ((uintptr_t)d.g) | ((uintptr_t)d.out)) & kDataAlign) == 0)) {
+            nfull = d.n / ROW;
+            vt = (nfull + BPW - 1) / BPW;
+        }
+        if (local < vt) {
+            if constexpr (LPB > 0) ste_vec_tile<LPB, V>(d.x, d.g, d.out, nfull, local, lane / LPB, lane % LPB, sm1, tie_mode, use_tab,
+                                                         tab);
+        } else {
+            const int64_t bkt = nfull + (local - vt);       // (a tile count that does not belong to this table reaches no bucket)
+            if (local >= 0 && bkt * row < d.n) ste_wave_bucket(d.x, d.g, d.out, d.n, row, bkt, lane, sm1, tie_mode);
         }
     }
 }
@@ -1194,6 +1269,42 @@ int qd_multi_uniform_f32(const QdTensorDesc* table, int ntensors, int64_t total_
         hipLaunchKernelGGL((k_multi_uniform<64>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
     else
         hipLaunchKernelGGL((k_multi_uniform<0>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
+    return check_launch();
+}
+
+int qd_multi_ste_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out) {
+    if (!host_table || ntensors <= 0 || bucket <= 0 || !total_tiles_out) return QD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < ntensors; ++i) {
+        const QdSteDesc& d = host_table[i];
+        if (d.n < 0 || (d.n > 0 && (!d.x || !d.g || !d.out))) return QD_ERR_INVALID_ARGUMENT;
+    }
+    int64_t tiles = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        host_table[i].first_tile = tiles;
+        tiles += ste_tiles(host_table[i], bucket);
+    }
+    *total_tiles_out = tiles;
+    return 0;
+}
+
+int qd_multi_ste_backward_f32(const QdSteDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, int levels,
+                              int tie_mode, void* stream) {
+    if (!table || ntensors <= 0 || total_tiles < 0 || bucket <= 0 || levels < 2) return QD_ERR_INVALID_ARGUMENT;
+    if (tie_mode != QD_STE_TIE_REFERENCE && tie_mode != QD_STE_TIE_TRUE_ARG) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = blocks_for(total_tiles, 4);
+    const float sm1 = (float)(levels - 1);
+#define QD_MULTI_STE(LPB, V)                                                                                        \
+    hipLaunchKernelGGL((k_multi_ste<LPB, V>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1, \
+                       tie_mode)
+    if (bucket == 64) QD_MULTI_STE(16, 1);              // the (LPB, V) of qd_ste_bucket_backward_f32
+    else if (bucket == 128) QD_MULTI_STE(16, 2);
+    else if (bucket == 256) QD_MULTI_STE(16, 4);
+    else if (bucket == 512) QD_MULTI_STE(64, 2);
+    else if (bucket == 1024) QD_MULTI_STE(64, 4);
+    else QD_MULTI_STE(0, 0);
+#undef QD_MULTI_STE
     return check_launch();
 }
 

@@ -1,4 +1,6 @@
-"""One-launch quantization of every parameter tensor of a model (multi-tensor K1).
+"""One-launch forms of the per-parameter loops of the training steps: quantization of every parameter tensor of a
+model (multi-tensor K1, below), differentiable quantization (MultiTensorDiffQuant) and the bucket-aware STE backward
+(MultiTensorSTE).
 
 The reference's training loops quantize parameter by parameter
 (cnn_models/conv_forward_model.py:235-247, translation_models/model.py:247-258):
@@ -202,3 +204,81 @@ class MultiTensorDiffQuant(object):
                                                        self.bucket_size, self.k, out.data_ptr(), self._scratch.data_ptr(),
                                                        self._scratch.numel() * 4, _lib.stream_ptr(self.device)))
         return out
+
+
+class MultiTensorSTE(object):
+    """The 'complicated' straight-through backward (ste.ste_bucket_backward, K7) of ALL quantized tensors of a model in
+    one launch (qd_multi_ste_backward_f32, include/qd_hip.h).
+
+    The reference calls quantizeFunctions[idx].backward(p.grad.data) parameter by parameter
+    (cnn_models/conv_forward_model.py:253-266).  Here the table of {weights, grad, out, numel} is built once;
+        backward(): grads[i] -> outs[i] for every i (in place by default: outs = grads)
+    `weights[i]` are the full-precision values the forward quantized.  Each result is bit-identical to
+    ste.ste_bucket_backward(weights[i], grads[i], bucket_size, s, out=outs[i], tie_mode=tie_mode).
+    """
+
+    def __init__(self, weights, grads, s, bucket_size, outs=None, tie_mode='reference'):
+        if bucket_size is None:                                                         # ref: quant_functions.py:332-334
+            raise NotImplementedError('Right now the code does not work with bucket_size None.'
+                                      ' Not hard to modify though')
+        if isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0:
+            raise ValueError('bucket_size must be a positive integer')
+        if int(s) != s or s < 2:
+            raise ValueError('s must be an integer >= 2')
+        if tie_mode not in ('reference', 'true_arg'):
+            raise ValueError("tie_mode must be 'reference' or 'true_arg'")
+        self.s, self.bucket_size = int(s), bucket_size
+        self.tie_mode = 0 if tie_mode == 'reference' else 1
+        # OWNING references: the device table holds raw pointers into these tensors
+        self.weights, self.grads = list(weights), list(grads)
+        self.outs = list(outs) if outs is not None else self.grads
+        if not self.weights:
+            raise ValueError('no tensors')
+        if len(self.grads) != len(self.weights) or len(self.outs) != len(self.weights):
+            raise ValueError('need one grad (and one out) per weight tensor')
+        for w, g, o in zip(self.weights, self.grads, self.outs):
+            for t, what in ((w, 'weights'), (g, 'grad'), (o, 'out')):
+                _lib.require_device_f32(t, what)
+                if not t.is_contiguous():
+                    raise ValueError('%s must be contiguous' % what)
+            if g.numel() != w.numel() or o.numel() != w.numel():
+                raise ValueError('grad and out must have as many elements as the weights')
+        self.device = self.weights[0].device
+        if any(t.device != self.device for ts in (self.weights, self.grads, self.outs) for t in ts):
+            raise ValueError('all tensors of a multi-tensor launch must live on one device')
+        self._table = None
+        self._ptrs = None
+        self._tiles = 0
+        self._plan()
+
+    def _plan(self):
+        n = len(self.weights)
+        host = (_lib.QdSteDesc * n)()
+        for i, (w, g, o) in enumerate(zip(self.weights, self.grads, self.outs)):
+            host[i].x = w.data_ptr()
+            host[i].g = g.data_ptr()
+            host[i].out = o.data_ptr()
+            host[i].n = w.numel()
+        tiles = ctypes.c_int64(0)
+        _lib.check(_lib.load().qd_multi_ste_plan(host, n, self.bucket_size, ctypes.byref(tiles)))
+        self._tiles = int(tiles.value)
+        self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
+        self._ptrs = [(w.data_ptr(), g.data_ptr(), o.data_ptr()) for w, g, o in zip(self.weights, self.grads, self.outs)]
+
+    def backward(self, check_pointers=True):
+        """out = the bucket-aware STE gradient for every tensor (one launch).  Returns the list of outs."""
+        if check_pointers:
+            for (pw, pg, po), w, g, o in zip(self._ptrs, self.weights, self.grads, self.outs):
+                if w.data_ptr() != pw or g.data_ptr() != pg or o.data_ptr() != po:
+                    self._plan()       # a held tensor's storage was swapped (set_, resize_): rebuild the table
+                    break
+        if self._tiles <= 0:
+            return self.outs
+        if _lib.on_other_device(self._table):        # launch with the tensors' device current
+            with torch.cuda.device(self.device):
+                return self.backward(check_pointers=False)
+        _lib.check(_lib.load().qd_multi_ste_backward_f32(self._table.data_ptr(), len(self.weights), self._tiles,
+                                                         self.bucket_size, self.s, self.tie_mode,
+                                                         _lib.stream_ptr(self.device)))
+        _lib.mark_written(self.outs)
+        return self.outs
