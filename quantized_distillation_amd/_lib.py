@@ -267,6 +267,13 @@ def on_other_device(t):
     return t.is_cuda and t.device.index is not None and t.device.index != torch.cuda.current_device()
 
 
+def upload_struct(obj, device):
+    """A ctypes structure, or an array of them, as a uint8 tensor on `device`: the descriptor tables and code books that the
+    kernels read from device memory."""
+    import torch
+    return torch.frombuffer(bytearray(bytes(obj)), dtype=torch.uint8).to(device)
+
+
 _host_scratch = None
 
 

@@ -23,7 +23,8 @@ def hipcc():
 def _headers():
     """What every object / assembly file depends on besides its own source (ONE list for build_extension and
     device_assembly: qd_transform.h holds almost all kernel code)."""
-    return [os.path.join(_lib.CSRC, 'qd_common.h'), os.path.join(_lib.CSRC, 'qd_transform.h'), os.path.join(_lib.INCLUDE, 'qd_hip.h'),
+    return [os.path.join(_lib.CSRC, 'qd_common.h'), os.path.join(_lib.CSRC, 'qd_transform.h'), os.path.join(_lib.CSRC, 'qd_multi.h'),
+            os.path.join(_lib.INCLUDE, 'qd_hip.h'),
             os.path.abspath(__file__)]
 
 
@@ -33,7 +34,7 @@ def _tmp(path):
     return '%s.tmp.%d' % (path, os.getpid())
 
 
-SOURCES = ['qd_kernels.hip', 'qd_nearest.hip', 'qd_reductions.hip', 'qd_scale.hip', 'qd_codec.hip', 'qd_multi_dq.hip', 'qd_abs.hip', 'qd_multi_global.hip',
+SOURCES = ['qd_kernels.hip', 'qd_nearest.hip', 'qd_reductions.hip', 'qd_scale.hip', 'qd_codec.hip', 'qd_multi_dq.hip', 'qd_abs.hip', 'qd_multi_uniform.hip',
            'qd_select.hip', 'qd_selftest.hip', 'qd_huffman.hip']
 OBJ_DIR = os.path.join(os.path.dirname(_lib.INCLUDE), 'build', 'obj')              # git-ignored; objects are rebuilt from source when stale
 

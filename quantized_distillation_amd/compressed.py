@@ -258,8 +258,8 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
         chunk_words = torch.empty(nchunks + 1, dtype=torch.int32, device=dev)
         words = torch.empty(max_words, dtype=torch.int32, device=dev)
         if cuda:
-            table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
-            code_d = torch.frombuffer(bytearray(bytes(code)), dtype=torch.uint8).to(dev)
+            table_d = _lib.upload_struct(table, dev)
+            code_d = _lib.upload_struct(code, dev)
             _lib.check(lib.qd_huffman_encode(table_d.data_ptr(), len(quant), nchunks, code_d.data_ptr(), chunk_words.data_ptr(),
                                              words.data_ptr(), max_words, st))
         else:
@@ -519,8 +519,8 @@ def _decode(f, data, res, device):
     code = canonical_code(f.lens, f.single)
     ptr = lambda x: x.data_ptr() if x.numel() else None      # noqa: E731
     if cuda:
-        table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
-        code_d = torch.frombuffer(bytearray(bytes(code)), dtype=torch.uint8).to(device)
+        table_d = _lib.upload_struct(table, device)
+        code_d = _lib.upload_struct(code, device)
         _lib.check(lib.qd_huffman_decode_f32(ptr(words), f.nwords, chunk_words.data_ptr(), table_d.data_ptr(), len(q), f.nchunks,
                                              code_d.data_ptr(), alpha.data_ptr(), beta.data_ptr(), ptr(pts),
                                              _lib.stream_ptr(device)))

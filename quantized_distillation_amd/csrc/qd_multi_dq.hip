@@ -8,6 +8,7 @@
 // do each sweep in ONE launch over a device table of per-tensor descriptors.  Arithmetic is
 // identical to qd_nearest_point_f32(prescaled, QD_ASSIGN_MIDPOINT) / qd_point_grad_f32.
 #include "qd_common.h"
+#include "qd_multi.h"
 #include "../../include/qd_hip.h"
 
 using namespace qd;
@@ -15,16 +16,6 @@ using namespace qd;
 namespace {
 
 constexpr int kMaxK = 64;
-
-__device__ __forceinline__ int find_owner(const QdDiffQuantDesc* table, int ntensors, int64_t item, bool by_block) {
-    int lo = 0, hi = ntensors - 1;                     // last tensor whose prefix <= item
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        const int64_t first = by_block ? table[mid].first_block : table[mid].first_tile;
-        if (first <= item) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // forward: a tile = 4 buckets of one tensor = one wave iteration; a DPP row owns a bucket
 template <int ROW>
@@ -34,10 +25,10 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
     __shared__ float s_mid[4][kMaxK];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int sub = lane >> 4, l = lane & 15;
-    const int64_t wave = uniform_wave_index();      // scalar: find_owner runs on s_load
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t t = wave; t < total_tiles; t += nwaves) {
-        const int ti = find_owner(table, ntensors, t, false);          // wave-uniform
+        const int ti = owner_of(table, ntensors, t);                   // wave-uniform
         const QdDiffQuantDesc d = table[ti];
         // this tensor's points and fp32 midpoints (quant_functions.py:533) into the wave's LDS slot;
         // LDS operations of one wave complete in order, the barriers only stop compiler reordering

@@ -1,0 +1,227 @@
+// qd_multi_uniform.hip -- multi-tensor uniform quantization (K9): the per-parameter loop of the training steps
+// (cnn_models/conv_forward_model.py:235-247) as one launch over a device table of QdTensorDesc.
+//   bucketed    qd_multi_plan, qd_multi_uniform_f32                 k_multi_uniform: bit-identical to qd_uniform_f32 per tensor
+//   no buckets  qd_multi_global_plan, qd_multi_uniform_global_f32   k_mg_*: bucket_size=None (e.g. cifar10_test.py:113), every
+//               tensor one bucket with its own global min/max.  The loop costs three launches per tensor through
+//               qd_uniform_f32 (reduce, fold, apply); here the whole model takes three launches in total.  Arithmetic
+//               identical to qd_uniform_f32(bucket = 0).
+#include "qd_transform.h"      // bucket_row16, KParams, Prep for k_multi_uniform; launch geometry
+#include "qd_multi.h"
+
+namespace {
+
+// ---- bucketed: one launch for every parameter of a model ---------------------------------------
+// A tile = 4 buckets of one tensor = one wave iteration; a DPP row owns a bucket.  Full, 16-byte
+// aligned 256-element buckets take the register path, everything else the row16 scalar path.
+template <int ROW>
+__global__ __launch_bounds__(256) void k_multi_uniform(const QdTensorDesc* __restrict__ table, int ntensors, int64_t total_tiles,
+                                                       int64_t bucket, float sm1) {
+    const int lane = threadIdx.x & 63;
+    const int sub = lane >> 4, l = lane & 15;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    Prep pp;
+    pp.mean = 0.0f;
+    pp.me = INFINITY;
+    const bool use_tab = sm1 <= 15.0f;
+    const float tab = (float)(lane & 15) / sm1;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const QdTensorDesc d = table[owner_of(table, ntensors, t)];
+        KParams p;
+        p.x = d.x; p.out = d.q; p.n = d.n;
+        p.row = d.n < bucket ? d.n : bucket;
+        p.nb = (d.n + p.row - 1) / p.row;
+        p.alpha = nullptr; p.beta = nullptr; p.mean = nullptr; p.me = INFINITY; p.sm1 = sm1; p.lev8 = nullptr;
+        p.idx = nullptr; p.idx_bytes = 0; p.pts = nullptr; p.k = 0; p.assign_mode = 0; p.prescaled = 0;
+        p.stochastic = 0; p.seed = 0; p.nvec = 0;
+        const int64_t bkt = (t - d.first_tile) * 4 + sub;
+        if (bkt >= p.nb) continue;
+        const int64_t lo = bkt * p.row;
+        const int64_t hi = lo + p.row < p.n ? lo + p.row : p.n;
+        const bool fast = ROW > 0 && (hi - lo) == ROW && p.row == ROW &&
+                          (((((uintptr_t)d.x) | ((uintptr_t)d.q)) & 15) == 0);
+        if (fast) {
+            constexpr int V = ROW > 0 ? ROW / 64 : 1;
+            const f4* src = (const f4*)(p.x + lo) + l;
+            f4 v[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = ldg_nt(src + j * 16);   // masters: read once
+            float mn = pmin4(v[0]), mx = pmax4(v[0]);      // NaN-propagating
+#pragma unroll
+            for (int j = 1; j < V; ++j) { mn = pmin(mn, pmin4(v[j])); mx = pmax(mx, pmax4(v[j])); }
+            mn = row16_min(mn); mx = row16_max(mx);
+            float a, b, lev;
+            alpha_beta(mn, mx, a, b);
+            f4* dst = (f4*)(p.out + lo) + l;
+            // rows of the wave that took this branch: all in the proven range -> bucket-invariant division (qd_common.h)
+            const bool fdiv = !__any(!fastdiv_ok(a));
+            auto body = [&](auto fast_c) {
+                constexpr bool FAST = decltype(fast_c)::value;
+                const float y = FAST ? 1.0f / a : 0.0f;
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    f4 r;
+                    if (use_tab) {                         // <= 16 levels: see k_bucket_vec (a DPP row is active as a whole here)
+                        r.x = qdq_tab<FAST>(v[j].x, a, b, sm1, 0.0f, lev, tab, y);
+                        r.y = qdq_tab<FAST>(v[j].y, a, b, sm1, 0.0f, lev, tab, y);
+                        r.z = qdq_tab<FAST>(v[j].z, a, b, sm1, 0.0f, lev, tab, y);
+                        r.w = qdq_tab<FAST>(v[j].w, a, b, sm1, 0.0f, lev, tab, y);
+                    } else {
+                        r.x = qdq<FAST>(v[j].x, a, b, sm1, 0.0f, lev, y);
+                        r.y = qdq<FAST>(v[j].y, a, b, sm1, 0.0f, lev, y);
+                        r.z = qdq<FAST>(v[j].z, a, b, sm1, 0.0f, lev, y);
+                        r.w = qdq<FAST>(v[j].w, a, b, sm1, 0.0f, lev, y);
+                    }
+                    stg_nt(r, dst + j * 16);
+                }
+            };
+            if (fdiv) body(std::true_type{}); else body(std::false_type{});
+        } else {
+            bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
+        }
+    }
+}
+
+// ---- no buckets ----------------------------------------------------------------------------------
+constexpr int kTile = 1024;     // elements per wave tile: 64 lanes x 4 float4
+
+// phase 1: per-tile min/max -> part[2*tile], part[2*tile+1]
+__global__ __launch_bounds__(256) void k_mg_minmax(const QdTensorDesc* __restrict__ table, int ntensors, int64_t total_tiles, float* part) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const QdTensorDesc d = table[owner_of(table, ntensors, t)];
+        const int64_t lo = (t - d.first_tile) * kTile;
+        const int64_t hi = lo + kTile < d.n ? lo + kTile : d.n;
+        float mn = INFINITY, mx = -INFINITY;
+        bool nan = false;
+        if (hi - lo == kTile && ((((uintptr_t)d.x) & 15) == 0)) {
+            const f4* src = (const f4*)(d.x + lo) + lane;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f4 v = ldg(src + j * 64);           // plain loads: phase 3 re-reads from L2 / MALL
+                mn = fminf(mn, fminf(fminf(v.x, v.y), fminf(v.z, v.w)));
+                mx = fmaxf(mx, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+                nan |= has_nan4(v);
+            }
+        } else {
+            for (int64_t i = lo + lane; i < hi; i += 64) { const float v = d.x[i]; mn = fminf(mn, v); mx = fmaxf(mx, v); nan |= (v != v); }
+        }
+        mn = wave_min(mn); mx = wave_max(mx);
+        if (group_any<64>(nan)) { mn = NAN; mx = NAN; }       // NaN poisons the tile and, in phase 2, the tensor
+        if (lane == 0) { part[2 * t] = mn; part[2 * t + 1] = mx; }
+    }
+}
+
+// phase 2: one block per tensor folds its tiles into (alpha, beta); the 1e-10 guard on the device
+__global__ __launch_bounds__(256) void k_mg_fold(const QdTensorDesc* __restrict__ table, int ntensors, int64_t total_tiles,
+                                                 const float* part, float* ab /* [ntensors][2] */) {
+    __shared__ float red[32];
+    const int ti = blockIdx.x;
+    const int64_t t0 = table[ti].first_tile;
+    const int64_t t1 = ti + 1 < ntensors ? table[ti + 1].first_tile : total_tiles;
+    float mn = INFINITY, mx = -INFINITY;
+    int nan = 0;
+    for (int64_t t = t0 + threadIdx.x; t < t1; t += 256) {
+        const float pm = part[2 * t];
+        nan |= (pm != pm);
+        mn = fminf(mn, pm); mx = fmaxf(mx, part[2 * t + 1]);
+    }
+    block_minmax(mn, mx, red);
+    if (__syncthreads_or(nan)) { mn = NAN; mx = NAN; }
+    if (threadIdx.x == 0) {
+        float a, b;
+        alpha_beta(mn, mx, a, b);
+        ab[2 * ti] = a; ab[2 * ti + 1] = b;
+    }
+}
+
+// phase 3: apply with the tensor's single (alpha, beta)
+__global__ __launch_bounds__(256) void k_mg_apply(const QdTensorDesc* __restrict__ table, int ntensors, int64_t total_tiles,
+                                                  const float* ab, float sm1) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdTensorDesc d = table[ti];
+        const float a = ab[2 * ti], b = ab[2 * ti + 1];
+        const int64_t lo = (t - d.first_tile) * kTile;
+        const int64_t hi = lo + kTile < d.n ? lo + kTile : d.n;
+        float lev;
+        if (hi - lo == kTile && (((((uintptr_t)d.x) | ((uintptr_t)d.q)) & 15) == 0)) {
+            const f4* src = (const f4*)(d.x + lo) + lane;
+            f4* dst = (f4*)(d.q + lo) + lane;
+            f4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ldg_nt(src + j * 64);
+            __builtin_amdgcn_sched_barrier(0);          // all four loads in flight before the first use
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f4 r;
+                r.x = qdq(v[j].x, a, b, sm1, 0.0f, lev); r.y = qdq(v[j].y, a, b, sm1, 0.0f, lev);
+                r.z = qdq(v[j].z, a, b, sm1, 0.0f, lev); r.w = qdq(v[j].w, a, b, sm1, 0.0f, lev);
+                stg_nt(r, dst + j * 64);
+            }
+        } else {
+            for (int64_t i = lo + lane; i < hi; i += 64) d.q[i] = qdq(d.x[i], a, b, sm1, 0.0f, lev);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t qd_multi_plan(QdTensorDesc* host_table, int ntensors, int64_t bucket) {
+    if (!host_table || ntensors < 0 || bucket <= 0) return -1;
+    return fill_prefix(host_table, ntensors, [bucket](const QdTensorDesc& d) -> int64_t {
+        if (d.n <= 0) return 0;
+        int64_t nb, row;
+        geometry(d.n, bucket, nb, row);
+        return (nb + 3) / 4;                             // a tile: 4 buckets
+    });
+}
+
+int qd_multi_uniform_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, int levels,
+                         void* stream) {
+    if (!table || ntensors <= 0 || total_tiles < 0 || bucket <= 0 || levels < 2) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = blocks_for(total_tiles, 4);
+    const float sm1 = (float)(levels - 1);
+    if (bucket == 256)
+        hipLaunchKernelGGL((k_multi_uniform<256>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
+    else if (bucket == 128)
+        hipLaunchKernelGGL((k_multi_uniform<128>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
+    else if (bucket == 64)
+        hipLaunchKernelGGL((k_multi_uniform<64>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
+    else
+        hipLaunchKernelGGL((k_multi_uniform<0>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
+    return check_launch();
+}
+
+int64_t qd_multi_global_plan(QdTensorDesc* host_table, int ntensors) {
+    if (!host_table || ntensors < 0) return -1;
+    return fill_prefix(host_table, ntensors, [](const QdTensorDesc& d) { return (d.n + kTile - 1) / kTile; });
+}
+
+int qd_multi_uniform_global_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int levels,
+                                float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!table || ntensors <= 0 || total_tiles < 0 || levels < 2 || !alpha_beta) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    if (!workspace || (((uintptr_t)workspace) & 15) || workspace_bytes < (size_t)total_tiles * 2 * sizeof(float))
+        return QD_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    int64_t b = (total_tiles + 3) / 4;
+    const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
+    hipLaunchKernelGGL(k_mg_minmax, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, part);
+    hipLaunchKernelGGL(k_mg_fold, dim3(ntensors), dim3(256), 0, st, table, ntensors, total_tiles, part, alpha_beta);
+    hipLaunchKernelGGL(k_mg_apply, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, alpha_beta,
+                       (float)(levels - 1));
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

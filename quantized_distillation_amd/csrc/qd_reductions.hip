@@ -5,9 +5,10 @@
 //   K6  qd_point_grad_f32        nonUniformQuantization_variable.backward     :471-506
 //   K7  qd_ste_bucket_backward_f32  uniformQuantization_variable.backward     :319-406
 //   K8  qd_clamp_f32, qd_truncated_ste_f32   the callers' 'truncated' STE     cnn_models/conv_forward_model.py:240-241,263-264
-//   K9  qd_multi_plan, qd_multi_uniform_f32  the per-parameter loop as one launch   conv_forward_model.py:235-247
+//   K7m qd_multi_ste_plan, qd_multi_ste_backward_f32  K7 of every parameter in one launch   conv_forward_model.py:253-266
 // Its own translation unit so that hipcc builds it next to qd_kernels.hip / qd_nearest.hip / qd_scale.hip (parallel build).
-#include "qd_transform.h"      // shared helpers: workspace carving, launch geometry, the per-bucket device routines K9 reuses
+#include "qd_transform.h"      // shared helpers: workspace carving, launch geometry
+#include "qd_multi.h"          // owner_of, fill_prefix for K7m
 
 namespace {
 
@@ -849,6 +850,55 @@ __global__ __launch_bounds__(256) void k_ste_backward(const float* x, const floa
     for (int64_t bkt = first + wave; bkt < nb; bkt += nwaves) ste_wave_bucket(x, g, out, n, row, bkt, lane, sm1, tie_mode);
 }
 
+// ---- K7: how a tensor is cut into the two bodies above -- the ONE statement of it ------------------
+// qd_ste_bucket_backward_f32 (its two launches), qd_multi_ste_plan (the tile count) and k_multi_ste (the tile -> bucket map)
+// all take it from ste_cut(), so a bucket is summed by the same body in the same order whichever entry point reaches it: that
+// is what makes the one-launch form bit-identical to the per-tensor call.
+//   * register path: when the bucket row is a row of QD_STE_SHAPES, the tensor has more than one bucket and x, g, out meet
+//     the data alignment (kDataAlign), the n / row full buckets go through ste_vec_tile<LPB, V>, 64 / LPB buckets per tile;
+//   * everything else -- the ragged last bucket after them, or every bucket of the tensor -- through ste_wave_bucket, one
+//     bucket per wave iteration.
+// X(row, lanes per bucket, float4 per lane): row = LPB x V x 4
+#define QD_STE_SHAPES(X)                                                                                              \
+    X(64, 16, 1)                                                                                                      \
+    X(128, 16, 2)                                                                                                     \
+    X(256, 16, 4) /* (32,2) and (64,1) lane groupings measured slower: 169-195 / 182-188 vs 166 us */                 \
+    X(512, 64, 2)                                                                                                     \
+    X(1024, 64, 4)
+
+constexpr int ste_lanes_per_bucket(int64_t row) {        // 0: no register path at this row
+#define QD_STE_LANES(ROW, LPB, V) if (row == ROW) return LPB;
+    QD_STE_SHAPES(QD_STE_LANES)
+#undef QD_STE_LANES
+    return 0;
+}
+
+struct SteCut {
+    int64_t row, nb;         // bucket row (the whole tensor when it is shorter than a bucket) and number of buckets
+    int64_t nfull;           // buckets [0, nfull) take the register path, [nfull, nb) ste_wave_bucket
+    int lpb;                 // lanes per bucket of the register path; 0: none
+    int64_t vtiles;          // its tiles: ceil(nfull / (64 / lpb))
+};
+// n > 0.  ROW says which rows may take the register path: -1 (the host callers) any row of the table; k_multi_ste<LPB, V>
+// passes its own LPB x V x 4 -- a launch has one bucket size -- so that the row stays a constant there (0: none).
+template <int ROW = -1>
+__host__ __device__ __forceinline__ SteCut ste_cut(const float* x, const float* g, const float* out, int64_t n, int64_t bucket) {
+    SteCut c;
+    c.row = n < bucket ? n : bucket;
+    c.nb = (n + c.row - 1) / c.row;
+    c.nfull = 0; c.lpb = 0; c.vtiles = 0;
+    const int lpb = ROW < 0 ? ste_lanes_per_bucket(c.row) : c.row == ROW ? ste_lanes_per_bucket(ROW) : 0;
+    const int64_t row = ROW > 0 ? ROW : c.row;              // (lpb > 0 under a ROW: it is the row)
+    // n > row: more than one bucket (nb > 1)
+    if (lpb > 0 && n > row && (((((uintptr_t)x) | ((uintptr_t)g) | ((uintptr_t)out)) & kDataAlign) == 0)) {
+        const int64_t bpw = 64 / lpb;
+        c.lpb = lpb;
+        c.nfull = n / row;
+        c.vtiles = (c.nfull + bpw - 1) / bpw;
+    }
+    return c;
+}
+
 // ---- K8: 'truncated' STE ----------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_clamp(float* w, int64_t n, float limit) {
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -896,139 +946,30 @@ __global__ __launch_bounds__(256) void k_truncated_ste(const float* w, float* gr
         if (fabsf(w[i]) > limit) grad[i] = 0.0f;
 }
 
-// ---- multi-tensor K1: one launch for every parameter of a model -------------------------------
-// A tile = 4 buckets of one tensor = one wave iteration; a DPP row owns a bucket.  Full, 16-byte
-// aligned 256-element buckets take the register path, everything else the row16 scalar path.
-template <int ROW>
-__global__ __launch_bounds__(256) void k_multi_uniform(const QdTensorDesc* __restrict__ table, int ntensors, int64_t total_tiles,
-                                                       int64_t bucket, float sm1) {
-    const int lane = threadIdx.x & 63;
-    const int sub = lane >> 4, l = lane & 15;
-    const int64_t wave = uniform_wave_index();      // scalar: the table search below runs on s_load
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    Prep pp;
-    pp.mean = 0.0f;
-    pp.me = INFINITY;
-    const bool use_tab = sm1 <= 15.0f;
-    const float tab = (float)(lane & 15) / sm1;
-    for (int64_t t = wave; t < total_tiles; t += nwaves) {
-        int lo_t = 0, hi_t = ntensors - 1;               // last tensor with first_tile <= t
-        while (lo_t < hi_t) {
-            const int mid = (lo_t + hi_t + 1) >> 1;
-            if (table[mid].first_tile <= t) lo_t = mid; else hi_t = mid - 1;
-        }
-        const QdTensorDesc d = table[lo_t];
-        KParams p;
-        p.x = d.x; p.out = d.q; p.n = d.n;
-        p.row = d.n < bucket ? d.n : bucket;
-        p.nb = (d.n + p.row - 1) / p.row;
-        p.alpha = nullptr; p.beta = nullptr; p.mean = nullptr; p.me = INFINITY; p.sm1 = sm1; p.lev8 = nullptr;
-        p.idx = nullptr; p.idx_bytes = 0; p.pts = nullptr; p.k = 0; p.assign_mode = 0; p.prescaled = 0;
-        p.stochastic = 0; p.seed = 0; p.nvec = 0;
-        const int64_t bkt = (t - d.first_tile) * 4 + sub;
-        if (bkt >= p.nb) continue;
-        const int64_t lo = bkt * p.row;
-        const int64_t hi = lo + p.row < p.n ? lo + p.row : p.n;
-        const bool fast = ROW > 0 && (hi - lo) == ROW && p.row == ROW &&
-                          (((((uintptr_t)d.x) | ((uintptr_t)d.q)) & 15) == 0);
-        if (fast) {
-            constexpr int V = ROW > 0 ? ROW / 64 : 1;
-            const f4* src = (const f4*)(p.x + lo) + l;
-            f4 v[V];
-#pragma unroll
-            for (int j = 0; j < V; ++j) v[j] = ldg_nt(src + j * 16);   // masters: read once
-            float mn = pmin4(v[0]), mx = pmax4(v[0]);      // NaN-propagating
-#pragma unroll
-            for (int j = 1; j < V; ++j) { mn = pmin(mn, pmin4(v[j])); mx = pmax(mx, pmax4(v[j])); }
-            mn = row16_min(mn); mx = row16_max(mx);
-            float a, b, lev;
-            alpha_beta(mn, mx, a, b);
-            f4* dst = (f4*)(p.out + lo) + l;
-            // rows of the wave that took this branch: all in the proven range -> bucket-invariant division (qd_common.h)
-            const bool fdiv = !__any(!fastdiv_ok(a));
-            auto body = [&](auto fast_c) {
-                constexpr bool FAST = decltype(fast_c)::value;
-                const float y = FAST ? 1.0f / a : 0.0f;
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    f4 r;
-                    if (use_tab) {                         // <= 16 levels: see k_bucket_vec (a DPP row is active as a whole here)
-                        r.x = qdq_tab<FAST>(v[j].x, a, b, sm1, 0.0f, lev, tab, y);
-                        r.y = qdq_tab<FAST>(v[j].y, a, b, sm1, 0.0f, lev, tab, y);
-                        r.z = qdq_tab<FAST>(v[j].z, a, b, sm1, 0.0f, lev, tab, y);
-                        r.w = qdq_tab<FAST>(v[j].w, a, b, sm1, 0.0f, lev, tab, y);
-                    } else {
-                        r.x = qdq<FAST>(v[j].x, a, b, sm1, 0.0f, lev, y);
-                        r.y = qdq<FAST>(v[j].y, a, b, sm1, 0.0f, lev, y);
-                        r.z = qdq<FAST>(v[j].z, a, b, sm1, 0.0f, lev, y);
-                        r.w = qdq<FAST>(v[j].w, a, b, sm1, 0.0f, lev, y);
-                    }
-                    stg_nt(r, dst + j * 16);
-                }
-            };
-            if (fdiv) body(std::true_type{}); else body(std::false_type{});
-        } else {
-            bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
-        }
-    }
-}
-
 // ---- multi-tensor K7: the 'complicated' STE backward of every parameter of a model in one launch ----
-// A tile = one wave iteration on one tensor.  Every tensor is cut exactly as qd_ste_bucket_backward_f32 cuts it, so that each
-// bucket is summed by the same body in the same order and the result is bit-identical to the per-tensor call:
-//   * register tiles: when the bucket row is 64 / 128 / 256 / 512 / 1024, the tensor has more than one bucket and x, g, out
-//     meet the data alignment (kDataAlign), the n / row full buckets go through ste_vec_tile<LPB, V>, 64 / LPB buckets per
-//     tile (4 up to row 256, 1 above) -- tiles 0 .. vt - 1 of the tensor, bucket t * (64 / LPB) + lane / LPB;
-//   * generic tiles: one bucket per tile through ste_wave_bucket -- the ragged last bucket after the register tiles (tile vt),
-//     or every bucket of the tensor (tile = bucket) when the register path does not apply.
-// ste_tiles() is that rule for the host plan; k_multi_ste<LPB, V> applies it with the row as a constant (a launch has ONE
-// bucket size, so at most one register instantiation; tensors shorter than a bucket are a single generic tile).
-inline int ste_lanes_per_bucket(int64_t row) {
-    return (row == 64 || row == 128 || row == 256) ? 16 : (row == 512 || row == 1024) ? 64 : 0;
-}
-inline int64_t ste_tiles(const QdSteDesc& d, int64_t bucket) {
-    if (d.n <= 0) return 0;
-    int64_t nb, row;
-    geometry(d.n, bucket, nb, row);
-    const int lpb = ste_lanes_per_bucket(row);
-    const bool aligned = (((((uintptr_t)d.x) | ((uintptr_t)d.g) | ((uintptr_t)d.out)) & kDataAlign) == 0) && nb > 1;
-    if (!lpb || !aligned) return nb;
-    const int64_t nfull = d.n / row, bpw = 64 / lpb;
-    return (nfull + bpw - 1) / bpw + (nb - nfull);
-}
-
+// A tile = one wave iteration on one tensor; ste_cut() says which: tiles 0 .. vtiles - 1 of a tensor are its register tiles
+// (bucket t * (64 / LPB) + lane / LPB), the tiles after them one bucket each from nfull on.  A launch has ONE bucket size, so
+// at most one register instantiation: k_multi_ste<LPB, V> is launched for the bucket size LPB x V x 4 (<0, 0>: any other).
 template <int LPB, int V>
 __global__ __launch_bounds__(256) void k_multi_ste(const QdSteDesc* __restrict__ table, int ntensors, int64_t total_tiles,
                                                    int64_t bucket, float sm1, int tie_mode) {
     constexpr int ROW = LPB * V * 4;                  // 0: no register path at this bucket size
-    constexpr int BPW = LPB > 0 ? 64 / LPB : 1;
     const int lane = threadIdx.x & 63;
-    const int64_t wave = uniform_wave_index();      // scalar: the table search below runs on s_load
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const bool use_tab = sm1 <= 15.0f;
     const float tab = (float)(lane & 15) / sm1;
     for (int64_t t = wave; t < total_tiles; t += nwaves) {
-        int lo_t = 0, hi_t = ntensors - 1;               // last tensor with first_tile <= t (an empty tensor owns no tile)
-        while (lo_t < hi_t) {
-            const int mid = (lo_t + hi_t + 1) >> 1;
-            if (table[mid].first_tile <= t) lo_t = mid; else hi_t = mid - 1;
-        }
-        const QdSteDesc d = table[lo_t];
+        const QdSteDesc d = table[owner_of(table, ntensors, t)];        // (an empty tensor owns no tile)
         if (d.n <= 0) continue;
         const int64_t local = t - d.first_tile;
-        const int64_t row = d.n < bucket ? d.n : bucket;
-        int64_t nfull = 0, vt = 0;
-        if (LPB > 0 && row == ROW && d.n > ROW &&
-            (((((uintptr_t)d.x) | ((uintptr_t)d.g) | ((uintptr_t)d.out)) & kDataAlign) == 0)) {
-            nfull = d.n / ROW;
-            vt = (nfull + BPW - 1) / BPW;
-        }
-        if (local < vt) {
-            if constexpr (LPB > 0) ste_vec_tile<LPB, V>(d.x, d.g, d.out, nfull, local, lane / LPB, lane % LPB, sm1, tie_mode, use_tab,
-                                                         tab);
+        const SteCut c = ste_cut<ROW>(d.x, d.g, d.out, d.n, bucket);
+        if (local < c.vtiles) {
+            if constexpr (LPB > 0) ste_vec_tile<LPB, V>(d.x, d.g, d.out, c.nfull, local, lane / LPB, lane % LPB, sm1, tie_mode,
+                                                         use_tab, tab);
         } else {
-            const int64_t bkt = nfull + (local - vt);       // (a tile count that does not belong to this table reaches no bucket)
-            if (local >= 0 && bkt * row < d.n) ste_wave_bucket(d.x, d.g, d.out, d.n, row, bkt, lane, sm1, tie_mode);
+            const int64_t bkt = c.nfull + (local - c.vtiles);   // (a tile count that does not belong to this table reaches no bucket)
+            if (local >= 0 && bkt * c.row < d.n) ste_wave_bucket(d.x, d.g, d.out, d.n, c.row, bkt, lane, sm1, tie_mode);
         }
     }
 }
@@ -1199,31 +1140,18 @@ int qd_ste_bucket_backward_f32(const float* x, const float* g, float* out, int64
     if (n < 0 || bucket <= 0 || levels < 2 || (n > 0 && (!x || !g || !out))) return QD_ERR_INVALID_ARGUMENT;
     if (tie_mode != QD_STE_TIE_REFERENCE && tie_mode != QD_STE_TIE_TRUE_ARG) return QD_ERR_INVALID_ARGUMENT;
     if (n == 0) return 0;
-    int64_t nb, row;
-    geometry(n, bucket, nb, row);
     hipStream_t st = (hipStream_t)stream;
     const float sm1 = (float)(levels - 1);
-    int64_t first = 0;                                   // buckets [0, first) take the register path
-    const bool aligned = (((((uintptr_t)x) | ((uintptr_t)g) | ((uintptr_t)out)) & kDataAlign) == 0) && nb > 1;
-    const int64_t nfull = n / row;
-#define QD_STE(LPB, V)                                                                                   \
-    {                                                                                                    \
-        first = nfull;                                                                                   \
-        const int64_t tiles = (nfull + (64 / LPB) - 1) / (64 / LPB);                                     \
-        hipLaunchKernelGGL((k_ste_backward_vec<LPB, V>), dim3(blocks_for(tiles, 4)), dim3(256), 0, st, x, g, \
-                           out, nfull, sm1, tie_mode);                                                   \
-    }
-    if (aligned && nfull > 0) {
-        if (row == 64) QD_STE(16, 1)
-        else if (row == 128) QD_STE(16, 2)
-        else if (row == 256) QD_STE(16, 4)      // (32,2) and (64,1) lane groupings measured slower: 169-195 / 182-188 vs 166 us
-        else if (row == 512) QD_STE(64, 2)
-        else if (row == 1024) QD_STE(64, 4)
-    }
-#undef QD_STE
-    if (first < nb)
-        hipLaunchKernelGGL(k_ste_backward, dim3(blocks_for(nb - first, 4)), dim3(256), 0, st, x, g, out, n, row, first,
-                           nb, sm1, tie_mode);
+    const SteCut c = ste_cut(x, g, out, n, bucket);
+#define QD_STE_LAUNCH(ROW, LPB, V)                                                                                       \
+    if (c.lpb > 0 && c.row == ROW)                                                                                       \
+        hipLaunchKernelGGL((k_ste_backward_vec<LPB, V>), dim3(blocks_for(c.vtiles, 4)), dim3(256), 0, st, x, g, out, c.nfull, \
+                           sm1, tie_mode);
+    QD_STE_SHAPES(QD_STE_LAUNCH)
+#undef QD_STE_LAUNCH
+    if (c.nfull < c.nb)
+        hipLaunchKernelGGL(k_ste_backward, dim3(blocks_for(c.nb - c.nfull, 4)), dim3(256), 0, st, x, g, out, n, c.row, c.nfull,
+                           c.nb, sm1, tie_mode);
     return check_launch();
 }
 
@@ -1242,48 +1170,17 @@ int qd_truncated_ste_f32(const float* w, float* grad, int64_t n, float limit, vo
     return check_launch();
 }
 
-int64_t qd_multi_plan(QdTensorDesc* host_table, int ntensors, int64_t bucket) {
-    if (!host_table || ntensors < 0 || bucket <= 0) return -1;
-    int64_t tiles = 0;
-    for (int i = 0; i < ntensors; ++i) {
-        int64_t nb, row;
-        geometry(host_table[i].n > 0 ? host_table[i].n : 1, bucket, nb, row);
-        host_table[i].first_tile = tiles;
-        tiles += host_table[i].n > 0 ? (nb + 3) / 4 : 0;
-    }
-    return tiles;
-}
-
-int qd_multi_uniform_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, int levels,
-                         void* stream) {
-    if (!table || ntensors <= 0 || total_tiles < 0 || bucket <= 0 || levels < 2) return QD_ERR_INVALID_ARGUMENT;
-    if (total_tiles == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const int blocks = blocks_for(total_tiles, 4);
-    const float sm1 = (float)(levels - 1);
-    if (bucket == 256)
-        hipLaunchKernelGGL((k_multi_uniform<256>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
-    else if (bucket == 128)
-        hipLaunchKernelGGL((k_multi_uniform<128>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
-    else if (bucket == 64)
-        hipLaunchKernelGGL((k_multi_uniform<64>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
-    else
-        hipLaunchKernelGGL((k_multi_uniform<0>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1);
-    return check_launch();
-}
-
 int qd_multi_ste_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out) {
     if (!host_table || ntensors <= 0 || bucket <= 0 || !total_tiles_out) return QD_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < ntensors; ++i) {
         const QdSteDesc& d = host_table[i];
         if (d.n < 0 || (d.n > 0 && (!d.x || !d.g || !d.out))) return QD_ERR_INVALID_ARGUMENT;
     }
-    int64_t tiles = 0;
-    for (int i = 0; i < ntensors; ++i) {
-        host_table[i].first_tile = tiles;
-        tiles += ste_tiles(host_table[i], bucket);
-    }
-    *total_tiles_out = tiles;
+    *total_tiles_out = fill_prefix(host_table, ntensors, [bucket](const QdSteDesc& d) -> int64_t {
+        if (d.n <= 0) return 0;
+        const SteCut c = ste_cut(d.x, d.g, d.out, d.n, bucket);
+        return c.vtiles + (c.nb - c.nfull);
+    });
     return 0;
 }
 
@@ -1295,16 +1192,14 @@ int qd_multi_ste_backward_f32(const QdSteDesc* table, int ntensors, int64_t tota
     hipStream_t st = (hipStream_t)stream;
     const int blocks = blocks_for(total_tiles, 4);
     const float sm1 = (float)(levels - 1);
-#define QD_MULTI_STE(LPB, V)                                                                                        \
-    hipLaunchKernelGGL((k_multi_ste<LPB, V>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1, \
-                       tie_mode)
-    if (bucket == 64) QD_MULTI_STE(16, 1);              // the (LPB, V) of qd_ste_bucket_backward_f32
-    else if (bucket == 128) QD_MULTI_STE(16, 2);
-    else if (bucket == 256) QD_MULTI_STE(16, 4);
-    else if (bucket == 512) QD_MULTI_STE(64, 2);
-    else if (bucket == 1024) QD_MULTI_STE(64, 4);
-    else QD_MULTI_STE(0, 0);
+#define QD_MULTI_STE(ROW, LPB, V)                                                                                        \
+    if (bucket == ROW)                                                                                                   \
+        hipLaunchKernelGGL((k_multi_ste<LPB, V>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1, \
+                           tie_mode);
+    QD_STE_SHAPES(QD_MULTI_STE)
 #undef QD_MULTI_STE
+    if (!ste_lanes_per_bucket(bucket))
+        hipLaunchKernelGGL((k_multi_ste<0, 0>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1, tie_mode);
     return check_launch();
 }
 

@@ -1,5 +1,5 @@
 """One-launch forms of the per-parameter loops of the training steps: quantization of every parameter tensor of a
-model (multi-tensor K1, below), differentiable quantization (MultiTensorDiffQuant) and the bucket-aware STE backward
+model (MultiTensorQuantizer), differentiable quantization (MultiTensorDiffQuant) and the bucket-aware STE backward
 (MultiTensorSTE).
 
 The reference's training loops quantize parameter by parameter
@@ -8,10 +8,9 @@ The reference's training loops quantize parameter by parameter
     for p in model.parameters():
         p.data = quantization.uniformQuantization(p.data, s, bucket_size=...)[0]
 
-With 22-110 tensors per model, most of them tiny, that is launch/host bound.  This class builds
-the table of {master pointer, shadow pointer, numel} once and quantizes the whole model with a
-single kernel launch per step (qd_multi_uniform_f32, include/qd_hip.h); the results are
-bit-identical to calling uniformQuantization on each tensor.
+With 22-110 tensors per model, most of them tiny, that is launch/host bound.  Each class here builds a device table of
+per-tensor descriptors {pointers, numel, work prefix} once (_DeviceTable) and runs the whole model with a single launch
+per step (include/qd_hip.h); the results are bit-identical to the per-tensor calls.
 """
 import ctypes
 
@@ -20,7 +19,79 @@ import torch
 from . import _lib
 
 
-class MultiTensorQuantizer(object):
+class _DeviceTable(object):
+    """What the one-launch classes share: the argument check, the descriptor table on the device, and the launch on a table
+    that is current.  A subclass names its descriptor type, says which tensors go into which field (_columns), calls the
+    library's plan (_plan_table) and makes the launch calls."""
+    _DESC = None           # the ctypes descriptor type (_lib.Qd*Desc)
+    _WATCH = ()            # attributes holding the tensors a caller may rebind: the table is rebuilt when one of them moved
+
+    def _adopt(self, first_contiguous=True, **named):
+        """named[what] = a sequence of tensors, one per tensor of the first sequence.  Returns them as lists of fp32 tensors on
+        one HIP device (self.device), each with as many elements as its counterpart in the first list and contiguous (the
+        first list too unless first_contiguous=False: tensors that are only read through a copy)."""
+        lists = [list(ts) for ts in named.values()]
+        if not lists[0]:
+            raise ValueError('no tensors')
+        if any(len(ts) != len(lists[0]) for ts in lists):
+            raise ValueError('%s: need one per tensor' % ', '.join(list(named)[1:]))
+        for what, ts in zip(named, lists):
+            for t, first in zip(ts, lists[0]):
+                _lib.require_device_f32(t, what)
+                if not t.is_contiguous() and (first_contiguous or ts is not lists[0]):
+                    raise ValueError('%s must be contiguous' % what)
+                if t.numel() != first.numel():
+                    raise ValueError('%s must match the tensors in size' % what)
+                if t.device != lists[0][0].device:
+                    raise ValueError('all tensors of a multi-tensor launch must live on one device')
+        self.device = lists[0][0].device
+        return lists
+
+    def _columns(self):
+        """((descriptor field, list of tensors), ...); the first column gives the element counts."""
+        raise NotImplementedError
+
+    def _plan_table(self, host, n):
+        """Call the library's plan on the host table (it fills the prefix fields), size the scratch; returns the tile count."""
+        raise NotImplementedError
+
+    def _held(self):
+        return [t.data_ptr() for name in self._WATCH for t in getattr(self, name)]
+
+    def _plan(self):
+        cols = self._columns()
+        self.n_tensors = n = len(cols[0][1])
+        host = (self._DESC * n)()
+        for i in range(n):
+            for field, ts in cols:
+                setattr(host[i], field, ts[i].data_ptr())
+            host[i].n = cols[0][1][i].numel()
+        self._tiles = self._plan_table(host, n)
+        self._table = _lib.upload_struct(host, self.device)
+        self._ptrs = self._held()
+
+    def _launch(self, call, written=None, check_pointers=True):
+        """_lib.check(call()) with the tensors' device current, on a table that points at the tensors held now.  `written`:
+        the held tensors the launch writes through the table; with zero tiles they have no element and nothing is launched."""
+        if check_pointers and self._held() != self._ptrs:
+            self._plan()                   # a held tensor's storage was swapped (p.data rebound, set_, resize_)
+        if written is not None and self._tiles <= 0:
+            return written
+        if _lib.on_other_device(self._table):
+            with torch.cuda.device(self.device):
+                return self._launch(call, written, check_pointers=False)
+        _lib.check(call())
+        if written is not None:
+            _lib.mark_written(written)     # one native call bumps their version counters
+        return written
+
+
+class MultiTensorQuantizer(_DeviceTable):
+    """uniformQuantization(t, s, bucket_size)[0] of every tensor, written to outputs[i], in one launch (qd_multi_uniform_f32;
+    bucket_size=None: three, qd_multi_uniform_global_f32, and `alpha_beta` holds every tensor's (alpha, beta))."""
+    _DESC = _lib.QdTensorDesc
+    _WATCH = ('inputs', 'outputs')
+
     def __init__(self, tensors, s, bucket_size, outputs=None):
         if bucket_size is not None and (not isinstance(bucket_size, int) or bucket_size <= 0):
             raise ValueError('bucket_size must be a positive integer or None')
@@ -28,72 +99,41 @@ class MultiTensorQuantizer(object):
             raise ValueError('s must be an integer >= 2')
         self.s = int(s)
         self.bucket_size = bucket_size
-        self.inputs = list(tensors)
-        if not self.inputs:
-            raise ValueError('no tensors')
-        for t in self.inputs:
-            _lib.require_device_f32(t)
-            if not t.is_contiguous():
-                raise ValueError('multi-tensor quantization needs contiguous tensors')
-        self.device = self.inputs[0].device
-        if any(t.device != self.device for t in self.inputs):
-            raise ValueError('all tensors of a multi-tensor launch must live on one device')
-        self.outputs = list(outputs) if outputs is not None else [torch.empty_like(t) for t in self.inputs]
-        if len(self.outputs) != len(self.inputs):
-            raise ValueError('need one output per input')
-        for t, o in zip(self.inputs, self.outputs):
-            _lib.require_device_f32(o, 'output')
-            if o.numel() != t.numel() or not o.is_contiguous() or o.device != t.device:
-                raise ValueError('outputs must match the inputs in size and device and be contiguous')
-        self._table = None
-        self._ptrs = None
-        self._tiles = 0
+        if outputs is None:
+            (self.inputs,) = self._adopt(tensors=tensors)
+            self.outputs = [torch.empty_like(t) for t in self.inputs]
+        else:
+            self.inputs, self.outputs = self._adopt(tensors=tensors, outputs=outputs)
         self._plan()
 
-    def _plan(self):
-        lib = _lib.load()
-        n = len(self.inputs)
-        host = (_lib.QdTensorDesc * n)()
-        for i, (t, o) in enumerate(zip(self.inputs, self.outputs)):
-            host[i].x = t.data_ptr()
-            host[i].q = o.data_ptr()
-            host[i].n = t.numel()
+    def _columns(self):
+        return ('x', self.inputs), ('q', self.outputs)
+
+    def _plan_table(self, host, n):
         if self.bucket_size is None:
-            self._tiles = int(lib.qd_multi_global_plan(host, n))
+            tiles = int(_lib.load().qd_multi_global_plan(host, n))
             self.alpha_beta = torch.empty(n, 2, dtype=torch.float32, device=self.device)     # per-tensor (alpha, beta)
-            self._scratch = torch.empty(max(4, 2 * self._tiles), dtype=torch.float32, device=self.device)
+            self._scratch = torch.empty(max(4, 2 * tiles), dtype=torch.float32, device=self.device)
         else:
-            self._tiles = int(lib.qd_multi_plan(host, n, self.bucket_size))
-        if self._tiles < 0:
+            tiles = int(_lib.load().qd_multi_plan(host, n, self.bucket_size))
+        if tiles < 0:
             raise RuntimeError('qd_multi_plan failed')
-        raw = bytes(host)
-        self._table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        self._ptrs = [(t.data_ptr(), o.data_ptr()) for t, o in zip(self.inputs, self.outputs)]
+        return tiles
+
+    def _call(self):
+        if self.bucket_size is None:
+            return _lib.load().qd_multi_uniform_global_f32(
+                self._table.data_ptr(), self.n_tensors, self._tiles, self.s, self.alpha_beta.data_ptr(),
+                self._scratch.data_ptr(), self._scratch.numel() * 4, _lib.stream_ptr(self.device))
+        return _lib.load().qd_multi_uniform_f32(self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s,
+                                                _lib.stream_ptr(self.device))
 
     def quantize(self, check_pointers=True):
         """Quantize all tensors (one launch).  Returns the list of output tensors."""
-        if check_pointers:
-            for (px, pq), t, o in zip(self._ptrs, self.inputs, self.outputs):
-                if t.data_ptr() != px or o.data_ptr() != pq:
-                    self._plan()       # storage moved (e.g. p.data was rebound): rebuild the table
-                    break
-        if self._tiles <= 0:
-            return self.outputs
-        if _lib.on_other_device(self._table):        # launch with the tensors' device current
-            with torch.cuda.device(self.device):
-                return self.quantize(check_pointers=False)
-        if self.bucket_size is None:
-            _lib.check(_lib.load().qd_multi_uniform_global_f32(
-                self._table.data_ptr(), len(self.inputs), self._tiles, self.s, self.alpha_beta.data_ptr(),
-                self._scratch.data_ptr(), self._scratch.numel() * 4, _lib.stream_ptr(self.device)))
-        else:
-            _lib.check(_lib.load().qd_multi_uniform_f32(self._table.data_ptr(), len(self.inputs), self._tiles,
-                                                        self.bucket_size, self.s, _lib.stream_ptr(self.device)))
-        _lib.mark_written(self.outputs)          # written through the device table: one native call bumps their version counters
-        return self.outputs
+        return self._launch(self._call, self.outputs, check_pointers)
 
 
-class MultiTensorDiffQuant(object):
+class MultiTensorDiffQuant(_DeviceTable):
     """Both per-step sweeps of differentiable quantization over ALL tensors of a model in one
     launch each (qd_multi_nearest_f32 / qd_multi_point_grad_f32, include/qd_hip.h).
 
@@ -105,6 +145,8 @@ class MultiTensorDiffQuant(object):
         backward(): gradients `grads[i]` -> grad of the points, [ntensors, k]
     Results are bit-identical (forward) / equal to rounding (backward) to the per-tensor calls.
     """
+    _DESC = _lib.QdDiffQuantDesc
+    _WATCH = ('outputs', 'grads')
 
     def __init__(self, tensors, outputs, grads, num_points, bucket_size):
         from .quantization.quant_functions import ScalingFunction
@@ -115,98 +157,56 @@ class MultiTensorDiffQuant(object):
         self.k, self.bucket_size = int(num_points), bucket_size
         # OWNING references: the device table below holds raw pointers into these tensors, so they are kept
         # alive here for the lifetime of the object.  A caller that rebinds `p.grad` (zero_grad(set_to_none=True))
-        # does not free them; backward() then reads the buffers given HERE, which is what check_pointers guards.
-        self.outputs, self.grads = list(outputs), list(grads)
-        self.device = tensors[0].device
+        # does not free them; backward() then reads the buffers given HERE, which is what the pointer check guards.
+        # (the tensors themselves are read once, by scale_down, which copies: any layout)
+        tensors, self.outputs, self.grads = self._adopt(False, tensors=tensors, outputs=outputs, grads=grads)
         self.scalings, self.scaled, self.indices = [], [], []
-        for t, o, g in zip(tensors, self.outputs, self.grads):
-            _lib.require_device_f32(t)
-            for other in (o, g):
-                _lib.require_device_f32(other)
-                if other.numel() != t.numel() or not other.is_contiguous():
-                    raise ValueError('outputs / grads must be contiguous and match the tensors in size')
-                if other.device != self.device:
-                    raise ValueError('all tensors of a multi-tensor launch must live on one device')
-            if t.device != self.device:
-                raise ValueError('all tensors of a multi-tensor launch must live on one device')
+        for t in tensors:
             sf = ScalingFunction('linear', False, False, bucket_size)
-            u = sf.scale_down(t).view(-1)[0:t.numel()].contiguous()
             self.scalings.append(sf)
-            self.scaled.append(u)
+            self.scaled.append(sf.scale_down(t).view(-1)[0:t.numel()].contiguous())
             self.indices.append(torch.empty(t.numel(), dtype=torch.uint8, device=self.device))
         self._plan()
 
-    def _plan(self):
-        bucket_size = self.bucket_size
-        n = len(self.scaled)
-        lib = _lib.load()
-        host = (_lib.QdDiffQuantDesc * n)()
-        for i in range(n):
-            host[i].u = self.scaled[i].data_ptr()
-            host[i].q = self.outputs[i].data_ptr()
-            host[i].idx = self.indices[i].data_ptr()
-            host[i].alpha = self.scalings[i].alpha.data_ptr()
-            host[i].beta = self.scalings[i].beta.data_ptr()
-            host[i].grad = self.grads[i].data_ptr()
-            host[i].n = self.scaled[i].numel()
-        blocks = ctypes.c_int64(0)
-        self._tiles = int(lib.qd_multi_dq_plan(host, n, bucket_size, ctypes.byref(blocks)))
-        self._blocks = int(blocks.value)
-        if self._tiles < 0:
+    def _columns(self):
+        return (('u', self.scaled), ('q', self.outputs), ('idx', self.indices), ('alpha', [sf.alpha for sf in self.scalings]),
+                ('beta', [sf.beta for sf in self.scalings]), ('grad', self.grads))
+
+    def _plan_table(self, host, n):
+        rows = ctypes.c_int64(0)
+        tiles = int(_lib.load().qd_multi_dq_plan(host, n, self.bucket_size, ctypes.byref(rows)))
+        if tiles < 0:
             raise RuntimeError('qd_multi_dq_plan failed')
-        self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
+        self._blocks = int(rows.value)             # partial rows of the gradient sweep
         self._scratch = torch.empty(max(1, self._blocks * self.k), dtype=torch.float32, device=self.device)
-        self.n_tensors = n
-        self._ptrs = [(o.data_ptr(), g.data_ptr()) for o, g in zip(self.outputs, self.grads)]
+        return tiles
 
     def rebind(self, outputs=None, grads=None):
         """Point the device table at new output / gradient buffers (e.g. after the caller re-allocated
         its gradients) -- one small H2D copy."""
-        if outputs is not None:
-            self.outputs = list(outputs)
-        if grads is not None:
-            self.grads = list(grads)
-        for u, o, g in zip(self.scaled, self.outputs, self.grads):
-            for other in (o, g):
-                _lib.require_device_f32(other)
-                if other.numel() != u.numel() or not other.is_contiguous() or other.device != self.device:
-                    raise ValueError('outputs / grads must be contiguous, on the same device and match the tensors in size')
+        _, self.outputs, self.grads = self._adopt(scaled=self.scaled, outputs=self.outputs if outputs is None else outputs,
+                                                  grads=self.grads if grads is None else grads)
         self._plan()
-
-    def _check(self):
-        for (po, pg), o, g in zip(self._ptrs, self.outputs, self.grads):
-            if o.data_ptr() != po or g.data_ptr() != pg:
-                self._plan()           # a held tensor's storage was swapped (set_, resize_): rebuild the table
-                break
 
     def forward(self, points):
         """points: [ntensors, k] fp32 device tensor, each row sorted.  Writes outputs[i] in place."""
         if points.shape != (self.n_tensors, self.k) or not points.is_contiguous():
             raise ValueError('points must be a contiguous [ntensors, k] tensor')
-        if _lib.on_other_device(self._table):
-            with torch.cuda.device(self.device):
-                return self.forward(points)
-        self._check()
-        _lib.check(_lib.load().qd_multi_nearest_f32(self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size,
-                                                    points.data_ptr(), self.k, _lib.stream_ptr(self.device)))
-        _lib.mark_written(self.outputs)
-        return self.outputs
+        return self._launch(lambda: _lib.load().qd_multi_nearest_f32(
+            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, points.data_ptr(), self.k,
+            _lib.stream_ptr(self.device)), self.outputs)
 
     def backward(self, out=None):
         """grad of the points from the gradient buffers given at construction: [ntensors, k]."""
         if out is None:
             out = torch.empty(self.n_tensors, self.k, dtype=torch.float32, device=self.device)
-        if _lib.on_other_device(self._table):
-            with torch.cuda.device(self.device):
-                return self.backward(out)
-        self._check()
-        _lib.check(_lib.load().qd_multi_point_grad_f32(self._table.data_ptr(), self.n_tensors, self._blocks,
-                                                       self.bucket_size, self.k, out.data_ptr(), self._scratch.data_ptr(),
-                                                       self._scratch.numel() * 4, _lib.stream_ptr(self.device)))
+        self._launch(lambda: _lib.load().qd_multi_point_grad_f32(
+            self._table.data_ptr(), self.n_tensors, self._blocks, self.bucket_size, self.k, out.data_ptr(),
+            self._scratch.data_ptr(), self._scratch.numel() * 4, _lib.stream_ptr(self.device)))
         return out
 
 
-class MultiTensorSTE(object):
+class MultiTensorSTE(_DeviceTable):
     """The 'complicated' straight-through backward (ste.ste_bucket_backward, K7) of ALL quantized tensors of a model in
     one launch (qd_multi_ste_backward_f32, include/qd_hip.h).
 
@@ -216,6 +216,8 @@ class MultiTensorSTE(object):
     `weights[i]` are the full-precision values the forward quantized.  Each result is bit-identical to
     ste.ste_bucket_backward(weights[i], grads[i], bucket_size, s, out=outs[i], tie_mode=tie_mode).
     """
+    _DESC = _lib.QdSteDesc
+    _WATCH = ('weights', 'grads', 'outs')
 
     def __init__(self, weights, grads, s, bucket_size, outs=None, tie_mode='reference'):
         if bucket_size is None:                                                         # ref: quant_functions.py:332-334
@@ -230,55 +232,23 @@ class MultiTensorSTE(object):
         self.s, self.bucket_size = int(s), bucket_size
         self.tie_mode = 0 if tie_mode == 'reference' else 1
         # OWNING references: the device table holds raw pointers into these tensors
-        self.weights, self.grads = list(weights), list(grads)
-        self.outs = list(outs) if outs is not None else self.grads
-        if not self.weights:
-            raise ValueError('no tensors')
-        if len(self.grads) != len(self.weights) or len(self.outs) != len(self.weights):
-            raise ValueError('need one grad (and one out) per weight tensor')
-        for w, g, o in zip(self.weights, self.grads, self.outs):
-            for t, what in ((w, 'weights'), (g, 'grad'), (o, 'out')):
-                _lib.require_device_f32(t, what)
-                if not t.is_contiguous():
-                    raise ValueError('%s must be contiguous' % what)
-            if g.numel() != w.numel() or o.numel() != w.numel():
-                raise ValueError('grad and out must have as many elements as the weights')
-        self.device = self.weights[0].device
-        if any(t.device != self.device for ts in (self.weights, self.grads, self.outs) for t in ts):
-            raise ValueError('all tensors of a multi-tensor launch must live on one device')
-        self._table = None
-        self._ptrs = None
-        self._tiles = 0
+        if outs is None:
+            self.weights, self.grads = self._adopt(weights=weights, grad=grads)
+            self.outs = self.grads
+        else:
+            self.weights, self.grads, self.outs = self._adopt(weights=weights, grad=grads, out=outs)
         self._plan()
 
-    def _plan(self):
-        n = len(self.weights)
-        host = (_lib.QdSteDesc * n)()
-        for i, (w, g, o) in enumerate(zip(self.weights, self.grads, self.outs)):
-            host[i].x = w.data_ptr()
-            host[i].g = g.data_ptr()
-            host[i].out = o.data_ptr()
-            host[i].n = w.numel()
+    def _columns(self):
+        return ('x', self.weights), ('g', self.grads), ('out', self.outs)
+
+    def _plan_table(self, host, n):
         tiles = ctypes.c_int64(0)
         _lib.check(_lib.load().qd_multi_ste_plan(host, n, self.bucket_size, ctypes.byref(tiles)))
-        self._tiles = int(tiles.value)
-        self._table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.device)
-        self._ptrs = [(w.data_ptr(), g.data_ptr(), o.data_ptr()) for w, g, o in zip(self.weights, self.grads, self.outs)]
+        return int(tiles.value)
 
     def backward(self, check_pointers=True):
         """out = the bucket-aware STE gradient for every tensor (one launch).  Returns the list of outs."""
-        if check_pointers:
-            for (pw, pg, po), w, g, o in zip(self._ptrs, self.weights, self.grads, self.outs):
-                if w.data_ptr() != pw or g.data_ptr() != pg or o.data_ptr() != po:
-                    self._plan()       # a held tensor's storage was swapped (set_, resize_): rebuild the table
-                    break
-        if self._tiles <= 0:
-            return self.outs
-        if _lib.on_other_device(self._table):        # launch with the tensors' device current
-            with torch.cuda.device(self.device):
-                return self.backward(check_pointers=False)
-        _lib.check(_lib.load().qd_multi_ste_backward_f32(self._table.data_ptr(), len(self.weights), self._tiles,
-                                                         self.bucket_size, self.s, self.tie_mode,
-                                                         _lib.stream_ptr(self.device)))
-        _lib.mark_written(self.outs)
-        return self.outs
+        return self._launch(lambda: _lib.load().qd_multi_ste_backward_f32(
+            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s, self.tie_mode,
+            _lib.stream_ptr(self.device)), self.outs, check_pointers)
