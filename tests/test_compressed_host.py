@@ -4,13 +4,13 @@ against the reference's own accounting (tests/golden/compressed_sizes.json), the
 files."""
 import json
 import os
-import struct
 
 import numpy as np
 import pytest
 import torch
 
 import quantization
+from huffman_cases import _npdecode, skewed_tensor
 from quantized_distillation_amd import compressed as C
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,72 +118,6 @@ def test_code_length_sum_equals_mean_bit_length_and_the_reference_size(tmp_path)
         assert rep['file_bytes'] <= case['size_mb'] * 1e6 + allowance, (case, rep)
 
 
-def _npdecode(path):
-    """An independent decoder of the format, written from DESIGN.md section 9 (numpy + Python only)."""
-    data = open(path, 'rb').read()
-    (magic, version, coding, mode, chunk, ntensors, max_len, single, table_bytes, nsym, nbuckets, npoints, nraw, nchunks,
-     nwords, crc, _r) = struct.unpack_from('<8sIIIIIIi7QII', data, 0)
-    assert magic == b'QDHUFF\x00\x01' and chunk == 1024
-    pos = 100
-    entries = []
-    for _ in range(ntensors):
-        ln, kind, ndim = struct.unpack_from('<HBB', data, pos)
-        pos += 4
-        name = data[pos:pos + ln].decode()
-        pos += ln
-        shape = struct.unpack_from('<%dQ' % ndim, data, pos)
-        pos += 8 * ndim
-        numel, bucket, levels, offset, count, first_point, first_chunk = struct.unpack_from('<QQIQQQQ', data, pos)
-        pos += 52
-        entries.append((name, kind, shape, numel, bucket, levels, offset, first_point, first_chunk))
-    o = 100 + table_bytes
-    lens = list(data[o:o + 256])
-    o += 256
-    alpha = np.frombuffer(data, '<f4', nbuckets, o); o += 4 * nbuckets
-    beta = np.frombuffer(data, '<f4', nbuckets, o); o += 4 * nbuckets
-    pts = np.frombuffer(data, '<f4', npoints, o); o += 4 * npoints
-    raw = np.frombuffer(data, '<f4', nraw, o); o += 4 * nraw
-    cw = np.frombuffer(data, '<u4', nchunks + 1 if nchunks else 0, o); o += 4 * len(cw)
-    words = np.frombuffer(data, '<u4', nwords, o)
-    bitstr = ''.join(format(int(w), '032b') for w in words)
-    # canonical code: (length, symbol) order
-    decode, code, prev = {}, 0, 0
-    for l, s in sorted((l, s) for s, l in enumerate(lens) if l):
-        code <<= (l - prev)
-        decode[format(code, '0%db' % l)] = s
-        code += 1
-        prev = l
-    out = {}
-    for name, kind, shape, numel, bucket, levels, offset, first_point, first_chunk in entries:
-        if kind != 1:
-            out[name] = raw[offset:offset + numel].reshape(shape)
-            continue
-        syms = []
-        for c in range(-(-numel // 1024)):
-            bits = bitstr[32 * int(cw[first_chunk + c]):]
-            cur, i = '', 0
-            while len(syms) < min(numel, 1024 * (c + 1)):
-                if single >= 0:
-                    syms.append(single)
-                    continue
-                cur += bits[i]
-                i += 1
-                if cur in decode:
-                    syms.append(decode[cur])
-                    cur = ''
-        y = np.empty(numel, np.float32)
-        for e, sym in enumerate(syms):
-            bk = offset + (e // bucket if bucket and numel >= bucket else 0)
-            a, b = alpha[bk], beta[bk]
-            if mode == 0:
-                v = np.float32(np.float32(sym) / np.float32(levels - 1)) * a
-            else:
-                v = pts[first_point + sym] * a
-            y[e] = np.float32(np.float32(v + b) + np.float32(0.0))
-        out[name] = y.reshape(shape)
-    return out
-
-
 @pytest.mark.parametrize('kind', ['uniform', 'nonuniform'])
 def test_an_independent_numpy_decoder_reads_the_documented_format(tmp_path, kind):
     ts = {'a': torch.randn(2100, generator=torch.Generator().manual_seed(5)), 'b': torch.randn(300), 'raw': torch.randn(9)}
@@ -212,6 +146,22 @@ def test_a_code_longer_than_32_bits_falls_back_to_fixed_width(tmp_path):
     assert rep['coding'] == 'fixed' and rep['max_code_length'] == 8 and C.read_header(p)['coding'] == 'fixed'
     assert rep['mean_bit_length'] > 0 and max(C.code_lengths(np.bincount(lev, minlength=256))[0]) > 32
     assert same(C.load_compressed(p)['w'], quantization.uniformQuantization(x, s)[0])
+
+
+def test_a_skewed_model_has_a_huffman_code_deeper_than_the_lookup_table(tmp_path):
+    # level counts 1, 1, 2, 4, ..., 2^19: every element lands on its intended level (tests/test_hip_compressed.py relies on
+    # it), the optimal code of the 21 levels is 20 bits deep and stays a Huffman code
+    x, lev, s = skewed_tensor()
+    q = quantization.uniformQuantization(x, s)[0]
+    assert same(q, x) and np.array_equal(np.rint(q.numpy().astype(np.float64) * (s - 1)).astype(np.int64), lev)
+    p = str(tmp_path / 'k.qd')
+    rep = C.save_compressed(p, {'w': x}, s=s, bucket_size=None)
+    counts = np.bincount(lev, minlength=256)
+    lens = C.read_header(p)['code_lengths']
+    assert rep['coding'] == 'huffman' and rep['max_code_length'] == 20 and C.read_header(p)['max_code_length'] == 20
+    assert sorted(l for l in lens if l) == sorted([20] + list(range(20, 0, -1)))
+    assert rep['code_bits'] == int(sum(int(c) * l for c, l in zip(counts, lens)))
+    assert same(C.load_compressed(p)['w'], q)
 
 
 def test_one_symbol_model_and_empty_model(tmp_path):
