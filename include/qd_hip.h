@@ -29,6 +29,29 @@
  *     (subtract_mean=True, quant_functions.py:66-68) and added back at the end (:148).
  *   - `clamp`/`max_element`: if clamp != 0, values are clamped to [-max_element, max_element]
  *     after the mean subtraction (quant_functions.py:72-74).
+ *
+ * NaN and +-inf in the inputs (both libraries, bit for bit; tests/test_hip_nonfinite.py, tests/test_nonfinite_host.py).  The
+ * rules are the reference's (torch's min / max propagate a NaN, numpy's searchsorted orders a NaN after every number):
+ *   - bucket statistics (qd_uniform_f32, qd_scale_down_f32, qd_nearest_point_f32 with prescaled == 0, qd_pack_uniform_f32,
+ *     qd_multi_uniform_f32, qd_multi_uniform_global_f32): a NaN anywhere in a bucket makes its alpha and beta NaN and with
+ *     them every output of THAT bucket -- no other bucket and, in a multi-tensor launch, no other tensor.  An infinity
+ *     needs no rule of its own: alpha = inf (or NaN, when the bucket holds nothing but one infinity) and beta = -inf go
+ *     through the same arithmetic -- u = (x - beta) / alpha is 0 or NaN, q is NaN or +-inf.
+ *   - level index (`level_idx` of qd_uniform_f32, the codes of qd_pack_uniform_f32, the symbols of a uniform checkpoint):
+ *     rint(u (levels - 1)) is an integer in [0, levels - 1] or NaN, never +-inf; a NaN level is stored as 0.  Unpacking such
+ *     a code gives NaN again through the bucket's alpha / beta.
+ *   - point index (qd_nearest_point_f32 in both assign modes and both idx widths, qd_multi_nearest_f32, the symbols of a
+ *     non-uniform checkpoint): a count of comparisons, hence in [0, k - 1] for every u; a NaN u takes the LAST point, k - 1.
+ *     +inf takes k - 1 and -inf takes 0 by the comparisons themselves.  `points` are expected finite and sorted.
+ *   - qd_inv_scale_f32, qd_unpack_uniform_f32, qd_huffman_decode_f32: plain IEEE u alpha + beta -- NaN / inf in u, alpha or
+ *     beta propagate (0 x inf = NaN, inf - inf = NaN).
+ *   - qd_point_grad_f32, qd_multi_point_grad_f32: every term g_i alpha_b is added to the bin of ITS index and to no other,
+ *     so a NaN / inf gradient element or bucket alpha poisons exactly the points whose index set holds such an element
+ *     (+inf and -inf on one point: NaN).
+ *   - qd_clamp_f32 leaves a NaN as it is and maps +-inf to +-limit (torch.clamp); qd_truncated_ste_f32 keeps the gradient
+ *     where w is NaN (|NaN| > limit is false) and zeroes it where w is +-inf.
+ *   - qd_ste_bucket_backward_f32, qd_multi_ste_backward_f32: a bucket of x that holds a NaN or an infinity quantizes to NaN
+ *     as a whole; out is NaN at the first such element (tie mode REFERENCE: at the bucket's first element) and g elsewhere.
  */
 #ifndef QD_HIP_H
 #define QD_HIP_H
@@ -119,7 +142,8 @@ int qd_inv_scale_f32(const float* u, float* y, int64_t n, int64_t bucket, const 
 
 /* First-occurrence arg-min / arg-max of each bucket, relative to the bucket start (int64), the
  * idx_min_rows / idx_max_rows of ScalingFunction (quant_functions.py:85-90,103-104).  Computed
- * on demand only (nothing on the per-step path reads them except the 'complicated' STE). */
+ * on demand only (nothing on the per-step path reads them except the 'complicated' STE).  A bucket that holds a NaN
+ * reports the position of its FIRST NaN for both, as torch.min / max(dim) do. */
 int qd_bucket_argminmax_f32(const float* x, int64_t n, int64_t bucket, const float* mean, int clamp,
                             float max_element, int64_t* argmin, int64_t* argmax, void* workspace,
                             size_t workspace_bytes, void* stream);
@@ -134,7 +158,8 @@ int qd_bucket_argminmax_f32(const float* x, int64_t n, int64_t bucket, const flo
  * strictly-closer-lower rule, :267-273) or QD_ASSIGN_MIDPOINT (#{midpoints <= u}, the
  * SearchSorted.query formulation, :531-573).
  * q: [n] = points[idx]*alpha + beta (+mean).  idx: optional, idx_bytes 8 (int64, what the
- * reference API returns) or 1 (uint8, k <= 256).
+ * reference API returns) or 1 (uint8, k <= 256).  A NaN u -- every element of a bucket whose alpha or beta is NaN --
+ * has index k - 1 (np.searchsorted orders a NaN last, :267-268 and :572) and value NaN.
  * Indices only (what SearchSorted.query returns, :531-563): prescaled != 0 with q == NULL and idx given -- n >= 4,
  * buckets of at least 4 elements (or bucket == 0), idx 16-byte (int64) / 4-byte (uint8) aligned; QD_ERR_INVALID_ARGUMENT
  * otherwise. */
@@ -157,7 +182,8 @@ int qd_ste_bucket_backward_f32(const float* x, const float* g, float* out, int64
                                int tie_mode, void* stream);
 
 /* K8: 'truncated' STE (cnn_models/conv_forward_model.py:240-241,263-264):
- * qd_clamp_f32: w = clamp(w, -limit, limit) in place; qd_truncated_ste_f32: grad[|w| > limit] = 0. */
+ * qd_clamp_f32: w = clamp(w, -limit, limit) in place (NaN stays NaN); qd_truncated_ste_f32: grad[|w| > limit] = 0 (a NaN w
+ * keeps its gradient, an infinite one loses it). */
 int qd_clamp_f32(float* w, int64_t n, float limit, void* stream);
 int qd_truncated_ste_f32(const float* w, float* grad, int64_t n, float limit, void* stream);
 

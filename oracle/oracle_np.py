@@ -107,7 +107,7 @@ def uniform_quantize(x, s, bucket=None, max_element=False, subtract_mean=False, 
     w = (r / sm1).astype(F32)                                     # :191
     q = inv_scale_down(w, sd['alpha'], sd['beta'], sd['mean'], sd['n'], sd['shape'])   # :193
     out = dict(sd)
-    out.update(q=q, lev=r.astype(np.int32))
+    out.update(q=q, lev=np.where(np.isnan(r), F32(0.0), r).astype(np.int32))   # NaN: level 0, what both libraries store
     return out
 
 

@@ -64,14 +64,15 @@ static void bucket_stats(const float* x, int64_t lo, int64_t hi, int sub_mean, f
                          float me, float* alpha, float* beta, int64_t* imin, int64_t* imax) {
     float mn = prep(x[lo], sub_mean, mean, clamp, me), mx = mn;
     int64_t jmn = 0, jmx = 0;
-    int has_nan = mn != mn;
+    int64_t jnan = mn != mn ? 0 : -1;      /* position of the bucket's FIRST NaN */
     for (int64_t i = lo + 1; i < hi; ++i) {
         float v = prep(x[i], sub_mean, mean, clamp, me);
-        if (v != v) has_nan = 1;
+        if (v != v && jnan < 0) jnan = i - lo;
         if (v < mn) { mn = v; jmn = i - lo; }
         if (v > mx) { mx = v; jmx = i - lo; }
     }
-    if (has_nan) { mn = NAN; mx = NAN; }   /* torch.min/max propagate NaN: the whole bucket becomes NaN */
+    /* torch.min/max propagate NaN: the whole bucket becomes NaN, and both report the position of its first NaN */
+    if (jnan >= 0) { mn = NAN; mx = NAN; jmn = jnan; jmx = jnan; }
     float a = mx - mn;
     if (a < QDO_TOL) a = 1.0f;
     *alpha = a; *beta = mn;
@@ -84,18 +85,15 @@ static void global_stats(const float* x, int64_t n, int sub_mean, float mean, in
                          float* alpha, float* beta, int64_t* imin, int64_t* imax) {
     float gmn = INFINITY, gmx = -INFINITY;
     int64_t gjmn = 0, gjmx = 0;
-    int any_nan = 0;
+    int64_t first_nan = INT64_MAX;         /* smallest position of a NaN: the same whatever the thread count */
 #pragma omp parallel
     {
         float mn = INFINITY, mx = -INFINITY;
-        int64_t jmn = INT64_MAX, jmx = INT64_MAX;
+        int64_t jmn = INT64_MAX, jmx = INT64_MAX, jnan = INT64_MAX;
 #pragma omp for schedule(static) nowait
         for (int64_t i = 0; i < n; ++i) {
             float v = prep(x[i], sub_mean, mean, clamp, me);
-            if (v != v) {
-#pragma omp atomic write
-                any_nan = 1;
-            }
+            if (v != v && jnan == INT64_MAX) jnan = i;      /* a thread's positions ascend: its first */
             if (v < mn) { mn = v; jmn = i; }
             if (v > mx) { mx = v; jmx = i; }
         }
@@ -103,9 +101,10 @@ static void global_stats(const float* x, int64_t n, int sub_mean, float mean, in
         {
             if (jmn != INT64_MAX && (mn < gmn || (mn == gmn && jmn < gjmn))) { gmn = mn; gjmn = jmn; }
             if (jmx != INT64_MAX && (mx > gmx || (mx == gmx && jmx < gjmx))) { gmx = mx; gjmx = jmx; }
+            if (jnan < first_nan) first_nan = jnan;
         }
     }
-    if (any_nan) { gmn = NAN; gmx = NAN; }
+    if (first_nan != INT64_MAX) { gmn = NAN; gmx = NAN; gjmn = first_nan; gjmx = first_nan; }
     float a = gmx - gmn;
     if (a < QDO_TOL) a = 1.0f;
     *alpha = a; *beta = gmn;
@@ -143,7 +142,7 @@ void qdo_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int s,
             float y = w * a;  y = y + b;            /* :142-143 */
             if (sub_mean) y = y + mean;             /* :148 (mean 0 is an exact no-op) */
             q[i] = y;
-            if (lev) lev[i] = (int32_t)r;
+            if (lev) lev[i] = r != r ? 0 : (int32_t)r;   /* NaN: level 0, what both libraries store (include/qd_hip.h) */
         }
         return;
     }
@@ -163,7 +162,7 @@ void qdo_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int s,
             float y = w * a;  y = y + b;
             if (sub_mean) y = y + mean;
             q[i] = y;
-            if (lev) lev[i] = (int32_t)r;
+            if (lev) lev[i] = r != r ? 0 : (int32_t)r;   /* NaN: level 0, what both libraries store (include/qd_hip.h) */
         }
     }
 }
@@ -202,6 +201,7 @@ void qdo_scale_down_f32(const float* x, float* u, int64_t n, int64_t bucket, flo
 /* nearest point, distance rule: searchsorted-left, clip, step down when STRICTLY closer to the
  * lower point.  quant_functions.py:267-273. */
 static inline int assign_distance(float u, const float* p, int k) {
+    if (u != u) return k - 1;         /* a NaN orders after every point (np.searchsorted): the last one */
     int lo = 0, hi = k;               /* first i with p[i] >= u */
     while (lo < hi) { int mid = (lo + hi) >> 1; if (p[mid] < u) lo = mid + 1; else hi = mid; }
     int i = lo > k - 1 ? k - 1 : lo;
@@ -211,6 +211,7 @@ static inline int assign_distance(float u, const float* p, int k) {
 
 /* midpoint rule: #{m_j <= u}, m_j = p_j + (p_{j+1}-p_j)/2 in fp32.  quant_functions.py:531-573. */
 static inline int assign_midpoint(float u, const float* m, int km1) {
+    if (u != u) return km1;           /* NaNs sort last in SearchSorted's sorted copy: final_indices[old_idx:] = k - 1 (:572) */
     int lo = 0, hi = km1;             /* first j with m[j] > u */
     while (lo < hi) { int mid = (lo + hi) >> 1; if (m[mid] <= u) lo = mid + 1; else hi = mid; }
     return lo;

@@ -358,7 +358,7 @@ int qd_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int leve
             float lev;
             const float v = pp(x[i]);
             q[i] = stochastic ? qdq_stochastic(v, a, b, sm1, pp.mean, philox_uniform(seed, i), lev) : qdq(v, a, b, sm1, pp.mean, lev);
-            if (level_idx) level_idx[i] = (uint8_t)(int)lev;                        // (NaN -> 0, as the device's conversion)
+            if (level_idx) level_idx[i] = lev != lev ? (uint8_t)0 : (uint8_t)(int)lev;   // a NaN level is stored as 0 (include/qd_hip.h)
         }
     };
     // a bucket's statistics need the whole bucket before any element of it is overwritten (in place): stats runs first

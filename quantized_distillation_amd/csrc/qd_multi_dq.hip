@@ -66,6 +66,7 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
 #define QD_ONE(c, n_)                                                         \
                 {                                                             \
                     id[n_] = count_before<true>(s_mid[w], k - 1, v[j].c);     \
+                    id[n_] = v[j].c != v[j].c ? k - 1 : id[n_];               /* a NaN orders last, as in qd_nearest_point_f32 */ \
                     float y = s_pts[w][id[n_]] * a;                           \
                     y = y + b;                                                \
                     r.c = y + 0.0f;                                           \
@@ -78,7 +79,8 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
             }
         } else {
             for (int64_t i = lo + l; i < hi; i += 16) {
-                const int id = count_before<true>(s_mid[w], k - 1, d.u[i]);
+                const float ui = d.u[i];
+                const int id = ui != ui ? k - 1 : count_before<true>(s_mid[w], k - 1, ui);
                 float y = s_pts[w][id] * a;
                 y = y + b;
                 d.q[i] = y + 0.0f;

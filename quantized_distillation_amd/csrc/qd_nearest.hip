@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_nearest_prescaled_stream(KParams p) {
             } else {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    id[c] = T->fine ? midpoint_index_fine(*T->s, uu[c]) : assign_point(*T->s, p.k, p.assign_mode, uu[c]);
+                    id[c] = T->fine ? midpoint_index_fine(*T->s, p.k, uu[c]) : assign_point(*T->s, p.k, p.assign_mode, uu[c]);
                     pt[c] = T->s->pts[id[c]];
                 }
             }

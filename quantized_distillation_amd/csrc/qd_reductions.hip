@@ -125,12 +125,16 @@ __global__ __launch_bounds__(256) void k_inv_scale(const float* u, float* y, int
 // ---- first-occurrence arg-min/arg-max per bucket (quant_functions.py:85-90) -------------------
 // key = (value, index) compared lexicographically; block per bucket; any size (single bucket of
 // a huge tensor is handled by a grid-stride over `chunks` partial blocks + a final fold).
+// A NaN is the minimum AND the maximum of its bucket, at its first position (torch.min / max(dim) propagate it, :85-90;
+// libqd_host.so does the same): a NaN candidate beats every number and a later NaN, a number never beats a NaN.
 struct ArgPair { float v; int64_t i; };
 __device__ __forceinline__ void arg_fold_min(float& v, int64_t& i, float ov, int64_t oi) {
-    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+    const bool on = ov != ov, cn = v != v;
+    if (on ? (!cn || oi < i) : (!cn && (ov < v || (ov == v && oi < i)))) { v = ov; i = oi; }
 }
 __device__ __forceinline__ void arg_fold_max(float& v, int64_t& i, float ov, int64_t oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    const bool on = ov != ov, cn = v != v;
+    if (on ? (!cn || oi < i) : (!cn && (ov > v || (ov == v && oi < i)))) { v = ov; i = oi; }
 }
 __device__ __forceinline__ void block_argminmax(float& mnv, int64_t& mni, float& mxv, int64_t& mxi, float* sv,
                                                 int64_t* si) {
@@ -174,8 +178,9 @@ __global__ __launch_bounds__(256) void k_argminmax(const float* x, int64_t n, in
         int64_t mni = INT64_MAX, mxi = INT64_MAX;
         for (int64_t i = clo + threadIdx.x; i < chi; i += blockDim.x) {
             const float v = prep(x[i], pp);
-            if (mni == INT64_MAX || v < mnv) { mnv = v; mni = i - lo; }   // strict: first occurrence wins
-            if (mxi == INT64_MAX || v > mxv) { mxv = v; mxi = i - lo; }
+            // strict: first occurrence wins; a thread that has met a NaN keeps it (its positions ascend), a NaN replaces a number
+            if (mni == INT64_MAX || (mnv == mnv && (v != v || v < mnv))) { mnv = v; mni = i - lo; }
+            if (mxi == INT64_MAX || (mxv == mxv && (v != v || v > mxv))) { mxv = v; mxi = i - lo; }
         }
         block_argminmax(mnv, mni, mxv, mxi, sv, si);
         if (threadIdx.x == 0) {

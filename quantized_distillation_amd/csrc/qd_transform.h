@@ -232,18 +232,21 @@ __device__ __forceinline__ void load_points(PointTable& C, PointStore& T, const 
 // is monotone), so the count is exact whatever the point distribution; with roughly uniform points
 // the remaining range holds 0-2 midpoints instead of k-1 (LDS reads per element: ~4 instead of ~9
 // at k = 256, and fewer bank conflicts).
-__device__ __forceinline__ int midpoint_index_fine(const PointStore& T, float u) {
+// A NaN u fails every comparison, which would count no midpoint (index 0); numpy's searchsorted, which the reference and
+// libqd_host.so follow, orders a NaN after every point: index k - 1.  One select per element says so on every path below.
+__device__ __forceinline__ int nan_last(float u, int k, int i) { return u != u ? k - 1 : i; }
+__device__ __forceinline__ int midpoint_index_fine(const PointStore& T, int k, float u) {
     const u32x2 e = T.cell[fine_cell_of(u)];
     const int s0 = (int)(e.x & 0xFFFFu), n_here = (int)(e.x >> 16);
     int i = s0 + ((__uint_as_float(e.y) <= u) ? 1 : 0);                   // right for a cell with 0 or 1 midpoints
     if (n_here > 1) i = s0 + count_before<true>(T.mid + s0, n_here, u);   // crowded cell: search inside it
-    return i;
+    return nan_last(u, k, i);
 }
 __device__ __forceinline__ int midpoint_index(const PointStore& T, int k, float u) {
-    if (k <= 32) return count_before<true>(T.mid, k - 1, u);
+    if (k <= 32) return nan_last(u, k, count_before<true>(T.mid, k - 1, u));
     const int c = cell_of(u);
     const int s0 = T.start[c];
-    return s0 + count_before<true>(T.mid + s0, T.start[c + 1] - s0, u);
+    return nan_last(u, k, s0 + count_before<true>(T.mid + s0, T.start[c + 1] - s0, u));
 }
 
 // nearest point of u (quant_functions.py:267-273 or :531-573)
@@ -263,7 +266,7 @@ __device__ __forceinline__ int assign_point(const PointStore& T, int k, int mode
         const float dh = fabsf(u - T.pts[i]);
         i -= (dl < dh) ? 1 : 0;                      // strictly closer to the lower point
     }
-    return i;
+    return nan_last(u, k, i);
 }
 
 // ---- per-element transform shared by every bucket kernel -----------------------------------
@@ -282,7 +285,7 @@ __device__ __forceinline__ float transform(const KParams& p, const PointTable* T
     } else {
         float u = v;
         if (!p.prescaled) { u = v - b; u = u / a; }
-        const int i = T->fine ? midpoint_index_fine(*T->s, u) : assign_point(*T->s, p.k, p.assign_mode, u);
+        const int i = T->fine ? midpoint_index_fine(*T->s, p.k, u) : assign_point(*T->s, p.k, p.assign_mode, u);
         const float pt = T->s->pts[i];
         side = (float)i;
         float y = pt * a;
@@ -302,6 +305,8 @@ __device__ __forceinline__ float transform(const KParams& p, const PointTable* T
 __device__ __forceinline__ void assign_point4(const PointStore& T, int k, int mode, const float (&u)[4], int (&i)[4]) {
     if (mode == QD_ASSIGN_MIDPOINT) {
         count_before4<true>(T.mid, k - 1, u, i);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) i[c] = nan_last(u[c], k, i[c]);
         return;
     }
     count_before4<false>(T.pts, k, u, i);                // searchsorted(side='left'): #{ points < u }
@@ -315,6 +320,7 @@ __device__ __forceinline__ void assign_point4(const PointStore& T, int k, int mo
         const float dl = fabsf(u[c] - pl[c]);
         const float dh = fabsf(u[c] - ph[c]);
         i[c] -= (i[c] > 0 && dl < dh) ? 1 : 0;           // strictly closer to the lower point
+        i[c] = nan_last(u[c], k, i[c]);
     }
 }
 

@@ -19,6 +19,8 @@ Outputs (all small, committed):
   ste.npz          patched 'complicated' backward
   nonuniform_options.npz   nonUniformQuantization with max_element / subtract_mean
   nonfinite.npz    uniformQuantization on inputs holding NaN / +-inf
+  nonfinite_paths.npz   the same inputs through nonUniformQuantization (+ variable, point gradient), scale_down ->
+                   inv_scale_down, clamp / truncated STE; run at 1 and 8 threads, only what agrees is stored
   misc.npz         scale_down / inv_scale_down round trips, initialize_quantization_points,
                    assign_bits_automatically, huffman mean bit length
   coords.npz       cart2hyperspherical / hypershperical2cart / invert_pytorch_vector / findFirstNonZeroIndex
@@ -27,7 +29,7 @@ Outputs (all small, committed):
                    reference run at several torch thread counts (its fp32 mean depends on them)
 
     python tests/golden/gen_golden.py [name ...]      only the named outputs (uniform, nonuniform, ste, misc,
-                                                      nonuniform_options, nonfinite, coords, big, mean_options)
+                                                      nonuniform_options, nonfinite, nonfinite_paths, coords, big, mean_options)
 """
 import inspect
 import json
@@ -416,6 +418,182 @@ def run_nonfinite():
     print('nonfinite cases:', len(meta))
 
 
+NONFINITE_PATTERNS = ('nan_full', 'nan_last', 'pinf', 'ninf', 'both', 'inf_bucket', 'ends')
+NONFINITE_N = 3000
+
+
+def plant_nonfinite(x, pattern, bucket):
+    """The seven non-finite inputs of nonfinite_paths.npz, planted into a copy of the finite base tensor x (n = 3000: with
+    bucket 256 eleven full buckets and a short last one of 184, with 100 thirty full ones, with None the single bucket)."""
+    x = x.clone()
+    n = x.numel()
+    nan, inf = float('nan'), float('inf')
+    if pattern == 'nan_full':
+        x[300] = nan                                   # a full bucket (1 of 256, 3 of 100)
+    elif pattern == 'nan_last':
+        x[n - 10] = nan                                # the short last bucket of 256 (the last full one of 100)
+    elif pattern == 'pinf':
+        x[700] = inf
+    elif pattern == 'ninf':
+        x[1500] = -inf
+    elif pattern == 'both':
+        x[1030], x[1040] = inf, -inf                   # one bucket at 256 (1024 ...) and at 100 (1000 ...)
+    elif pattern == 'inf_bucket':
+        row = bucket or 256
+        x[2 * row:3 * row] = inf                       # a whole bucket of +inf: max - min = inf - inf = NaN
+    elif pattern == 'ends':
+        x[0], x[n - 1] = nan, nan
+    else:
+        raise ValueError(pattern)
+    return x
+
+
+def _bname(bucket):
+    return 'b%s' % ('none' if bucket is None else bucket)
+
+
+def _expand(v, bucket, n):
+    """Per-bucket values (alpha, beta) repeated over the elements of their bucket, unpadded."""
+    v = v.reshape(-1)
+    return np.repeat(v, bucket)[:n] if (bucket is not None and n >= bucket) else np.full(n, v[0], np.float32)
+
+
+def _nonfinite_paths_once():
+    """Everything nonfinite_paths.npz holds, computed by the reference at the current thread count: {key: array}.  Arrays of
+    the seven patterns are stacked (they differ in a bucket or two, so the stack compresses to little more than one of
+    them); what follows from stored arrays by one fp32 operation per reference op is checked here and not stored: the
+    quantized values q = points[idx] * alpha + beta (quant_functions.py:278, 142-143), and the results of the pre-processed
+    path and of the plain variable's backward where they equal the plain function's / the pre-processed backward's."""
+    out = {}
+    n = NONFINITE_N
+    # few distinct values (the integers -2 .. 2): the arrays derived from it compress to a few KB, and ties abound
+    base = (torch.randint(-2, 3, (n,), generator=gen(31000)).float()).contiguous()
+    base[0::97] = -2.0
+    base[1::97] = 2.0
+    g = (torch.randint(-4, 5, (n,), generator=gen(31001)).float() / 4.0).contiguous()
+    out['base'], out['g'] = base.numpy(), g.numpy()
+    np_same = lambda a_, b_: a_.shape == b_.shape and a_.tobytes() == b_.tobytes()      # noqa: E731
+    # scale_down -> inv_scale_down (K2 / K3); alpha / beta of a (bucket, pattern) serve the nearest-point cases too
+    scale = []
+    for bucket in (256, 100, None):
+        rows = {'u': [], 'alpha': [], 'beta': [], 'back': []}
+        for pat in NONFINITE_PATTERNS:
+            x = plant_nonfinite(base, pat, bucket)
+            sf = refq.ScalingFunction('linear', False, False, bucket)
+            u = sf.scale_down(x)
+            rows['u'].append(u.numpy().reshape(-1).copy())
+            rows['alpha'].append(sf.alpha.numpy().reshape(-1).copy())
+            rows['beta'].append(sf.beta.numpy().reshape(-1).copy())
+            rows['back'].append(sf.inv_scale_down(u).numpy().reshape(-1).copy())
+            scale.append(dict(bucket=bucket, pattern=pat, u_shape=list(u.shape), alpha_shape=list(sf.alpha.shape)))
+        for key, v in rows.items():
+            out['%s_%s' % (key, _bname(bucket))] = np.stack(v)
+    cases = []
+    for k in (2, 4, 16):
+        pts = torch.sort(torch.rand(k, generator=gen(31100 + k)))[0].float().contiguous()
+        out['pts_k%d' % k] = pts.numpy()
+        for bucket in (256, 100, None):
+            idxs, gps = [], []
+            for j, pat in enumerate(NONFINITE_PATTERNS):
+                c = dict(k=k, bucket=bucket, pattern=pat)
+                x = plant_nonfinite(base, pat, bucket)
+                try:
+                    q, idx, sf = refq.nonUniformQuantization(x, pts, bucket_size=bucket)
+                    fn = refq.nonUniformQuantization_variable(bucket_size=bucket, pre_process_tensors=True, tensor=x)
+                    q_pre = fn.forward(None, pts).clone()
+                    idx_pre = fn.savedForBackward['indices'].clone()
+                    _, gp = fn.backward(g)
+                    fn_np = refq.nonUniformQuantization_variable(bucket_size=bucket)
+                    q_v = fn_np.forward(x, pts)
+                    _, gp_np = fn_np.backward(g)
+                except Exception as e:                                      # noqa: BLE001 -- the rule of the header then pins the case
+                    c['raises'] = '%s: %s' % (type(e).__name__, e)
+                    cases.append(c)
+                    idxs.append(np.zeros(n, np.uint8))
+                    gps.append(np.zeros(k, np.float32))
+                    continue
+                name = _bname(bucket)
+                assert np_same(sf.alpha.numpy().reshape(-1), out['alpha_' + name][j]) and np_same(sf.beta.numpy().reshape(-1), out['beta_' + name][j])
+                with np.errstate(invalid='ignore'):
+                    derived = ((pts.numpy()[idx.numpy()] * _expand(out['alpha_' + name][j], bucket, n)).astype(np.float32)
+                               + _expand(out['beta_' + name][j], bucket, n)).astype(np.float32)
+                # everything the reference returns beyond idx and gp follows from them: checked, not stored
+                assert np.array_equal(derived, q.numpy(), equal_nan=True), c
+                assert torch.equal(idx_pre, idx) and np.array_equal(q_pre.numpy(), q.numpy(), equal_nan=True), c
+                assert np.array_equal(q_v.numpy(), q.numpy(), equal_nan=True) and np_same(gp_np.numpy(), gp.numpy()), c
+                idxs.append(idx.numpy().astype(np.uint8))
+                gps.append(gp.numpy())
+                cases.append(c)
+            out['idx_k%d_%s' % (k, _bname(bucket))] = np.stack(idxs)
+            out['gp_k%d_%s' % (k, _bname(bucket))] = np.stack(gps)
+    # the two epilogues of the training loop (cnn_models/conv_forward_model.py:240-241, 263-264) on w holding NaN, +-inf and
+    # +-limit exactly, next to values just inside and just outside
+    one = np.float32(1.0)
+    w = (torch.randint(-12, 13, (300,), generator=gen(31002)).float() / 8.0).contiguous()
+    special = [float('nan'), float('inf'), float('-inf'), 1.0, -1.0, float(np.nextafter(one, np.float32(2))),
+               float(np.nextafter(one, np.float32(0))), -float(np.nextafter(one, np.float32(2))), -float(np.nextafter(one, np.float32(0))),
+               0.0, -0.0]
+    for j, v in enumerate(special):
+        w[7 + 13 * j] = v
+    w[0], w[299] = float('nan'), float('-inf')
+    gw = (torch.randint(-16, 17, (300,), generator=gen(31003)).float() / 8.0 + 0.0625).contiguous()
+    clamped = w.clone().clamp_(-1, 1)
+    gt = gw.clone()
+    gt[w.abs() > 1] = 0
+    out['e_w'], out['e_g'], out['e_clamped'], out['e_truncated'] = w.numpy(), gw.numpy(), clamped.numpy(), gt.numpy()
+    # point gradients: a finite tensor, a gradient that holds one NaN / one +inf / a +inf and a -inf on the same point
+    grads = []
+    for bucket in (256, 100, None):
+        fn = refq.nonUniformQuantization_variable(bucket_size=bucket, pre_process_tensors=True, tensor=base)
+        pts = torch.from_numpy(out['pts_k4'])
+        fn.forward(None, pts)
+        idx = fn.savedForBackward['indices'].view(-1)
+        same = torch.nonzero(idx == idx[1234]).view(-1)
+        pair = (1234, int(same[same > 2000][0]))                   # two elements on one point, in different buckets
+        gps = []
+        for name, plant in (('nan', {411: float('nan')}), ('pinf', {1777: float('inf')}),
+                            ('pair', {pair[0]: float('inf'), pair[1]: float('-inf')})):
+            gg = g.clone()
+            for pos, v in plant.items():
+                gg[pos] = v
+            fn.forward(None, pts)
+            _, gp = fn.backward(gg)
+            gps.append(gp.numpy())
+            grads.append(dict(bucket=bucket, kind=name, k=4, plant=[[int(p_), repr(float(v))] for p_, v in plant.items()]))
+        out['fin_idx_' + _bname(bucket)] = idx.numpy().astype(np.uint8)
+        out['fin_alpha_' + _bname(bucket)] = fn.scaling_function.alpha.numpy().reshape(-1)
+        out['fin_gp_' + _bname(bucket)] = np.stack(gps)
+    return out, dict(n=n, patterns=list(NONFINITE_PATTERNS), cases=cases, scale=scale, grads=grads)
+
+
+def run_nonfinite_paths():
+    """NaN / +-inf on the paths beyond uniformQuantization: nonUniformQuantization and its pre-processed variable form (forward
+    indices and values, point gradient), scale_down -> inv_scale_down, the clamp / truncated-STE epilogues, and point
+    gradients of a finite tensor under a non-finite gradient.  The reference is run at 1 and at 8 torch threads; an array that
+    differs between the two runs is NOT stored (its key is listed in meta['unstable'] and printed), the case is then pinned by
+    the device == host == oracle rule of include/qd_hip.h instead of by the golden."""
+    runs = {}
+    for th in (1, 8):
+        torch.set_num_threads(th)
+        runs[th] = _nonfinite_paths_once()
+    torch.set_num_threads(1)
+    (a, meta), (b, meta_b) = runs[1], runs[8]
+    assert meta == meta_b and sorted(a) == sorted(b)
+    unstable = [key for key in sorted(a) if not (a[key].shape == b[key].shape and a[key].tobytes() == b[key].tobytes())]
+    for key in unstable:
+        del a[key]
+        print('nonfinite_paths: %s differs between 1 and 8 threads -- not stored' % key)
+    meta['unstable'] = unstable
+    raised = [c for c in meta['cases'] if 'raises' in c]
+    for c in raised:
+        print('nonfinite_paths: the reference raises on', c)
+    a['meta'] = np.array(json.dumps(meta))
+    path = os.path.join(HERE, 'nonfinite_paths.npz')
+    np.savez_compressed(path, **a)
+    print('nonfinite_paths: %d nearest-point cases (%d raise), %d scale cases, %d gradient cases, %d unstable arrays, %d bytes'
+          % (len(meta['cases']), len(raised), len(meta['scale']), len(meta['grads']), len(unstable), os.path.getsize(path)))
+
+
 def run_coords():
     """The hyperspherical-coordinate helpers of help_functions.py:8-64 (not on the quantization path; kept
     for a complete module surface).  Vectors with trailing zeros, a single non-zero head, all zeros, a
@@ -520,6 +698,6 @@ def run_mean_options():
 
 if __name__ == '__main__':
     todo = dict(uniform=run_uniform, nonuniform=run_nonuniform, ste=run_ste, misc=run_misc, nonuniform_options=run_nonuniform_options,
-                nonfinite=run_nonfinite, coords=run_coords, big=run_big, mean_options=run_mean_options)
+                nonfinite=run_nonfinite, nonfinite_paths=run_nonfinite_paths, coords=run_coords, big=run_big, mean_options=run_mean_options)
     for name in (sys.argv[1:] or list(todo)):
         todo[name]()

@@ -202,3 +202,26 @@ def test_truncated_or_corrupted_files_raise_value_error(tmp_path):
         open(q, 'wb').write(b)
         with pytest.raises(ValueError):
             C.load_compressed(q)
+
+
+@pytest.mark.parametrize('mode', ['uniform', 'nonuniform'])
+def test_model_with_nan_and_infinite_buckets_round_trips(tmp_path, mode):
+    """The CPU half of tests/test_hip_nonfinite.py::test_compressed_checkpoint_of_a_model_with_nonfinite_buckets: a model with
+    a NaN bucket, a +inf bucket and a -inf bucket is not refused; it decodes to exactly the tensors the quantizer gives, NaN
+    buckets included (a NaN level is stored as symbol 0, a NaN's point index as k - 1, and the NaN / inf alpha and beta
+    stored with the bucket reproduce the value), and writing it twice gives the same bytes."""
+    from nonfinite_cases import nonfinite_model, same as same_nan
+    ts = nonfinite_model()
+    pts = torch.tensor([0.0, 0.3, 0.6, 1.0])
+    kw = dict(s=16) if mode == 'uniform' else dict(points=[pts] * 3)
+    p, p2 = str(tmp_path / 'm.qd'), str(tmp_path / 'm2.qd')
+    rep = C.save_compressed(p, ts, bucket_size=256, **kw)
+    C.save_compressed(p2, ts, bucket_size=256, **kw)
+    assert rep['coding'] == 'huffman' and open(p, 'rb').read() == open(p2, 'rb').read()
+    out = C.load_compressed(p)
+    for k, t in ts.items():
+        want = (quantization.uniformQuantization(t, 16, bucket_size=256)[0] if mode == 'uniform'
+                else quantization.nonUniformQuantization(t, pts, bucket_size=256)[0])
+        assert torch.isnan(want).any() and not torch.isnan(want).all()
+        assert same_nan(out[k], want.numpy()), k
+        assert same_nan(_npdecode(p)[k], want.numpy()), k

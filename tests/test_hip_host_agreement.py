@@ -64,6 +64,51 @@ def test_device_and_host_library_agree(n, bucket):
     assert not torch.equal(qh, quantization.uniformQuantization(x, 16, bucket_size=bucket)[0])      # (and it IS the stochastic branch)
 
 
+@pytest.mark.parametrize('bucket', [256, 100, None, 33])
+def test_device_and_host_library_agree_on_nonfinite_inputs(bucket):
+    """test_device_and_host_library_agree on the non-finite inputs of tests/golden/nonfinite_paths.npz (3000 elements): the
+    same bits from both libraries on every per-call path -- values, alpha / beta, arg indices, point indices, scaling and its
+    inverse, the epilogues; a NaN where the other has a NaN.  The point gradients: non-finite bins by position and sign, the
+    finite ones both within the suite's bound of the float64 sums."""
+    import errlog
+    from nonfinite_cases import G, PATTERNS, plant, same
+    from oracle import oracle_np as onp
+    P = G()
+    gn = torch.from_numpy(P.g)
+
+    def agree(a_, b_):
+        return same(a_, b_.detach().cpu().numpy())
+    for pat in PATTERNS:
+        xn = torch.from_numpy(plant(P.base, pat, bucket))
+        xnd = xn.to(DEV)
+        for s in (16, 2, 256):
+            qc, sc = quantization.uniformQuantization(xn, s, bucket_size=bucket)
+            qd, sd = quantization.uniformQuantization(xnd, s, bucket_size=bucket)
+            assert agree(qd, qc) and agree(sd.alpha, sc.alpha) and agree(sd.beta, sc.beta), (pat, s)
+            assert torch.equal(sd.idx_min_rows.cpu(), sc.idx_min_rows) and torch.equal(sd.idx_max_rows.cpu(), sc.idx_max_rows), (pat, s)
+        for k in (2, 4, 16):
+            pk = torch.from_numpy(P.pts(k))
+            qc, ic, sfc = quantization.nonUniformQuantization(xn, pk, bucket_size=bucket)
+            qd, idv, _ = quantization.nonUniformQuantization(xnd, pk, bucket_size=bucket)
+            assert agree(qd, qc) and torch.equal(idv.cpu(), ic), (pat, k)
+            fc = quantization.nonUniformQuantization_variable(bucket_size=bucket, pre_process_tensors=True, tensor=xn)
+            fd = quantization.nonUniformQuantization_variable(bucket_size=bucket, pre_process_tensors=True, tensor=xnd)
+            assert agree(fd.forward(None, pk.to(DEV)), fc.forward(None, pk)), (pat, k)
+            assert torch.equal(fd.savedForBackward['indices'].cpu(), fc.savedForBackward['indices']), (pat, k)
+            gpc, gpd = fc.backward(gn)[1].numpy(), fd.backward(gn.to(DEV))[1].cpu().numpy()
+            with np.errstate(invalid='ignore'):
+                want, absum = onp.point_grad(P.g, fc.savedForBackward['indices'].numpy(), sfc.alpha.numpy(), bucket, k)
+            fin = np.isfinite(want)
+            for got in (gpc, gpd):
+                assert np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(got[np.isinf(want)], want[np.isinf(want)]), (pat, k, got, want)
+                errlog.check_sum('K6 point gradient, device and host on non-finite inputs', got[fin], want[fin], absum[fin], (pat, k, bucket), n_terms=P.g.size)
+        a, b = quantization.ScalingFunction('linear', False, False, bucket), quantization.ScalingFunction('linear', False, False, bucket)
+        uc, ud = a.scale_down(xn), b.scale_down(xnd)
+        assert agree(ud, uc) and agree(b.inv_scale_down(ud), a.inv_scale_down(uc)), pat
+        assert agree(ste.clamp_(xn.clone().to(DEV), 1.0), ste.clamp_(xn.clone(), 1.0)), pat
+        assert agree(ste.truncated_ste_(gn.clone().to(DEV), xnd, 1.0), ste.truncated_ste_(gn.clone(), xn, 1.0)), pat
+
+
 @pytest.mark.parametrize('tie_mode', [0, 1])        # QD_STE_TIE_REFERENCE, QD_STE_TIE_TRUE_ARG
 def test_ste_backward_on_buckets_that_hold_a_nan_or_an_infinity(tie_mode):
     """torch's min / max propagate a NaN and report it at its FIRST position, for the minimum and the maximum alike.  A bucket

@@ -680,8 +680,7 @@ def test_fine_cell_table_with_crowded_and_degenerate_points(k):
         mid = (pts[:-1] + (pts[1:] - pts[:-1]) / np.float32(2.0)).astype(np.float32)          # :533, fp32
         uu = u.copy()
         uu[4000:4000 + mid.size] = mid                                                         # values ON midpoints: ties go up
-        want_idx = np.searchsorted(mid, uu, side='right').astype(np.int64)
-        want_idx[np.isnan(uu)] = 0
+        want_idx = np.searchsorted(mid, uu, side='right').astype(np.int64)         # (a NaN orders last: k - 1, as in the reference)
         want_q = pts[want_idx]
         pd, ud = dev(pts), dev(uu)
         for bucket, nn in ((256, n), (1000, n), (100, n), (33, n), (0, n), (0, 50000), (256, 700), (5000, n)):

@@ -26,6 +26,9 @@ settings.register_profile('qd', derandomize=(SOAK == 1), database=None)
 settings.load_profile('qd')
 
 
+NONFINITE = 9                                     # the `kind` of make() that plants NaN / +-inf
+
+
 def make(n, seed, kind):
     rng = np.random.RandomState(seed)
     if kind == 0:
@@ -49,21 +52,28 @@ def make(n, seed, kind):
         with np.errstate(over='ignore', under='ignore'):
             e = np.repeat(rng.randint(-140, 120, size=n // 97 + 1), 97)[:n]
             x = np.ldexp(rng.randn(n), e)
+    elif kind == NONFINITE:
+        # NaN, +inf and -inf at seeded positions, the first and the last element among them; no nan_to_num below
+        x = rng.randn(n)
+        where = np.unique(np.concatenate([[0, n - 1], rng.randint(0, n, size=4)]))
+        x[where] = np.array([np.nan, np.inf, -np.inf])[rng.randint(0, 3, size=where.size)]
+        x[0] = np.nan if n < 3 else x[0]
+        return x.astype(np.float32)
     else:
         x = np.where(rng.rand(n) < 0.6, 0.0, rng.randn(n) * 1e-40) + (rng.rand(n) < 0.001) * 1.0   # zeros, denormals, a few ones
     return np.nan_to_num(x.astype(np.float32), nan=0.0, posinf=3e38, neginf=-3e38)
 
 
 @settings(max_examples=60 * SOAK, deadline=None, suppress_health_check=list(HealthCheck))
-@given(n=sizes, bucket=buckets, s=levels, seed=st.integers(0, 2 ** 31 - 1), kind=st.integers(0, 8),
+@given(n=sizes, bucket=buckets, s=levels, seed=st.integers(0, 2 ** 31 - 1), kind=st.integers(0, 9),
        clamp=st.sampled_from([False, False, 0.5, 2.0]))
 def test_uniform_matches_oracle(n, bucket, s, seed, kind, clamp):
     x = make(n, seed, kind)
     q, sf = quantization.uniformQuantization(torch.from_numpy(x).to(DEV), s, bucket_size=bucket, max_element=clamp)
     r = oc.uniform_quantize(x, s, bucket, max_element=clamp)
-    assert np.array_equal(q.cpu().numpy(), r['q'])
-    assert np.array_equal(sf.alpha.cpu().numpy().reshape(-1), r['alpha'])
-    assert np.array_equal(sf.beta.cpu().numpy().reshape(-1), r['beta'])
+    assert np.array_equal(q.cpu().numpy(), r['q'], equal_nan=True)
+    assert np.array_equal(sf.alpha.cpu().numpy().reshape(-1), r['alpha'], equal_nan=True)
+    assert np.array_equal(sf.beta.cpu().numpy().reshape(-1), r['beta'], equal_nan=True)
     assert np.array_equal(sf.idx_min_rows.cpu().numpy().reshape(-1), r['imin'])
     assert np.array_equal(sf.idx_max_rows.cpu().numpy().reshape(-1), r['imax'])
 
@@ -96,7 +106,7 @@ def test_nonuniform_matches_oracle(n, bucket, k, seed, kind, dup):
 @settings(max_examples=30 * SOAK, deadline=None, suppress_health_check=list(HealthCheck))
 @given(n=sizes, bucket=st.sampled_from([64, 128, 256, 256, 512, 1024, 2048, None, 100, 33, 7, 3, 1000, 513, 4096, 5003]),
        sb=st.sampled_from([(2, 1), (3, 2), (4, 2), (9, 4), (16, 4), (16, 8), (256, 8)]),
-       seed=st.integers(0, 2 ** 31 - 1), kind=st.integers(0, 5))
+       seed=st.integers(0, 2 ** 31 - 1), kind=st.sampled_from([0, 1, 2, 3, 4, 5, NONFINITE]))
 def test_pack_unpack_matches_quantizer(n, bucket, sb, seed, kind):
     from quantized_distillation_amd import codec
     s, bits = sb
@@ -104,7 +114,7 @@ def test_pack_unpack_matches_quantizer(n, bucket, sb, seed, kind):
     xd = torch.from_numpy(x).to(DEV)
     pk = codec.pack_uniform(xd, s, bucket, bits=bits)
     q, _ = quantization.uniformQuantization(xd, s, bucket_size=bucket)
-    assert torch.equal(pk.unpack(), q)
+    assert np.array_equal(pk.unpack().cpu().numpy(), q.cpu().numpy(), equal_nan=True)
     r = oc.uniform_quantize(x, s, bucket)
     assert np.array_equal(codec.level_histogram(xd, s, bucket).cpu().numpy(), np.bincount(r['lev'], minlength=s))
 
@@ -140,12 +150,13 @@ def test_ste_backward_matches_oracle(n, bucket, s, seed, kind):
 @settings(max_examples=25 * SOAK, deadline=None, suppress_health_check=list(HealthCheck))
 @given(sizes_=st.lists(st.one_of(st.integers(1, 300), st.integers(300, 70000)), min_size=1, max_size=12),
        bucket=st.sampled_from([None, 256, 256, 64, 128, 100, 7, 1024]), s=st.sampled_from([2, 4, 16, 256]),
-       seed=st.integers(0, 2 ** 31 - 1), kind=st.integers(0, 5), misalign=st.booleans())
+       seed=st.integers(0, 2 ** 31 - 1), kind=st.integers(0, 6), misalign=st.booleans())
 def test_multi_tensor_matches_oracle(sizes_, bucket, s, seed, kind, misalign):
     """One launch over a random set of tensors (carved out of one flat buffer, optionally at odd element
     offsets so that some bases are not 16-byte aligned) == the oracle on each tensor."""
     from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer
-    xs = [make(n, seed + 13 * i, (kind + i) % 6) for i, n in enumerate(sizes_)]
+    kinds = (0, 1, 2, 3, 4, 5, NONFINITE)
+    xs = [make(n, seed + 13 * i, kinds[(kind + i) % 7]) for i, n in enumerate(sizes_)]
     gap = 3 if misalign else 0
     total = sum(n + gap for n in sizes_)
     flat_in = torch.zeros(total, device=DEV)
@@ -160,7 +171,7 @@ def test_multi_tensor_matches_oracle(sizes_, bucket, s, seed, kind, misalign):
     mt.quantize()
     for x, o in zip(xs, outs):
         r = oc.uniform_quantize(x, s, bucket, want_idx=False, want_lev=False)
-        assert np.array_equal(o.cpu().numpy(), r['q'])
+        assert np.array_equal(o.cpu().numpy(), r['q'], equal_nan=True)
     if gap:                                                            # nothing written between the tensors
         keep = torch.ones(total, dtype=torch.bool)
         off = 0

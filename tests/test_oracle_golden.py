@@ -192,3 +192,48 @@ def test_mean_options_oracle_reproduces_every_reference_run():
             step = float(np.abs(x).max()) / c['s'] / 4
             whole_level += sum(int((np.abs(a.astype(np.float64) - b) > step).sum()) for b in rest)
     assert self_disagreements >= 5 and whole_level > 1000
+
+
+def test_nonfinite_paths_golden():
+    """tests/golden/nonfinite_paths.npz (the reference at 1 and at 8 threads, identical at both): NaN / +-inf through the
+    nearest-point forward in both assignment rules, the point gradient, scale_down -> inv_scale_down and the two epilogues.
+    A NaN takes the LAST point (np.searchsorted orders it after everything); a non-finite gradient term poisons its own
+    point and no other."""
+    from nonfinite_cases import G
+    from oracle import oracle_c as oc
+    P = G()
+    meta, z = P.meta, P.z
+    assert meta['unstable'] == [] and len(meta['cases']) == 63 and not any('raises' in c for c in meta['cases'])
+    eq = lambda a, b: np.array_equal(np.asarray(a).reshape(-1), np.asarray(b).reshape(-1), equal_nan=True)     # noqa: E731
+    oc.build()
+
+    def grad_matches(impl, g, idx, alpha, bucket, k, gold, tag):
+        want, absum = impl.point_grad(g, idx, alpha, bucket, k)
+        fin = np.isfinite(gold)
+        assert np.array_equal(np.isnan(want), np.isnan(gold)) and np.array_equal(want[np.isinf(gold)], gold[np.isinf(gold)]), (tag, want, gold)
+        errlog.check_sum('oracle point gradient vs the reference, non-finite inputs', gold[fin], want[fin], absum[fin], tag)
+    with np.errstate(invalid='ignore'):
+        for i in range(len(meta['cases'])):
+            c = P.nearest(i)
+            for impl in (onp, oc):
+                for mode in ('distance', 'midpoint'):           # the reference's two paths agreed on every case
+                    r = impl.nonuniform_quantize(c['x'], c['pts'], c['bucket'], mode=mode)
+                    assert eq(r['idx'], c['idx']) and eq(r['q'], c['q']), (i, c['pattern'], impl.__name__, mode)
+                    assert eq(r['alpha'], c['alpha']) and eq(r['beta'], c['beta']), (i, c['pattern'])
+                grad_matches(impl, P.g, c['idx'], c['alpha'], c['bucket'], c['k'], c['gp'], (i, impl.__name__))
+        for i in range(len(meta['scale'])):
+            c = P.scale(i)
+            sd = onp.scale_down(c['x'], c['bucket'])
+            assert eq(sd['u'], c['u']) and eq(sd['alpha'], c['alpha']) and eq(sd['beta'], c['beta']), (c['bucket'], c['pattern'])
+            assert eq(onp.inv_scale_down(sd['u'], sd['alpha'], sd['beta'], sd['mean'], sd['n'], sd['shape']), c['back'])
+            assert eq(oc.scale_down(c['x'], c['bucket'])['u'], c['u'].reshape(-1)[:c['x'].size]), (c['bucket'], c['pattern'])
+        for i in range(len(meta['grads'])):
+            c = P.grad(i)
+            for impl in (onp, oc):
+                grad_matches(impl, c['g'], c['idx'], c['alpha'], c['bucket'], 4, c['gp'], (i, impl.__name__))
+    w, gw = z['e_w'], z['e_g']
+    assert eq(onp.truncated_ste_mask(w, gw), z['e_truncated'])
+    with np.errstate(invalid='ignore'):
+        cl = np.where(w > 1, np.float32(1), w)
+        cl = np.where(cl < -1, np.float32(-1), cl)
+    assert eq(cl, z['e_clamped'])
