@@ -39,7 +39,9 @@
  *     through the same arithmetic -- u = (x - beta) / alpha is 0 or NaN, q is NaN or +-inf.
  *   - level index (`level_idx` of qd_uniform_f32, the codes of qd_pack_uniform_f32, the symbols of a uniform checkpoint):
  *     rint(u (levels - 1)) is an integer in [0, levels - 1] or NaN, never +-inf; a NaN level is stored as 0.  Unpacking such
- *     a code gives NaN again through the bucket's alpha / beta.
+ *     a code gives NaN again through the bucket's alpha / beta.  The stochastic branch of qd_uniform_f32 can reach level
+ *     `levels`, one past the top (see there): its level index SATURATES at levels - 1, so the stored index is in
+ *     [0, levels - 1] on every path and fits its byte at levels == 256.
  *   - point index (qd_nearest_point_f32 in both assign modes and both idx widths, qd_multi_nearest_f32, the symbols of a
  *     non-uniform checkpoint): a count of comparisons, hence in [0, k - 1] for every u; a NaN u takes the LAST point, k - 1.
  *     +inf takes k - 1 and -inf takes 0 by the comparisons themselves.  `points` are expected finite and sorted.
@@ -121,7 +123,15 @@ int qd_mean_f32(const float* x, int64_t n, float* mean_out, void* workspace, siz
  * 1 B written per element; deterministic rounding without mean / clamp, bucket in {64, 128, 256, 512, 1024, 2048}, x 16-byte
  * aligned (the geometry of qd_pack_uniform_f32, whose 8-bit form this is); QD_ERR_UNSUPPORTED otherwise.
  * stochastic != 0 selects the stochastic-rounding branch (:174-187) with a counter-based
- * in-kernel generator keyed by (seed, element index).
+ * in-kernel generator keyed by (seed, element index): Philox4x32 with 7 rounds, counter = (element >> 2 as two words,
+ * 0x51ed270b, 0x2545f491), key = seed (low word, high word), element e takes word e & 3; the draw is the word's top 24 bits
+ * times 2^-24, in [0, 1).  With t = u (levels - 1), l = floor(t), p = t - l the element goes to level l + 1 where
+ * draw <= p and to level l otherwise -- "<=" as the reference (:187), so an element exactly on a level (p == 0: each
+ * bucket's minimum and maximum) still moves up when its draw is exactly 0.0, once in 2^24 draws, and the bucket's maximum
+ * then comes out at level `levels`, ONE PAST THE TOP: q = ((levels - 1) / (levels - 1) + 1 / (levels - 1)) alpha + beta,
+ * as the reference computes it.  level_idx is saturated at levels - 1 there (it keeps its documented range; at
+ * levels == 256 the value 256 has no byte to go to).  The seed is a by-value launch argument: a captured launch replays
+ * the same draws (the Python layer refuses a stochastic call during stream capture for that reason).
  * workspace is only used when the tensor is a single bucket (bucket == 0 or n < bucket). */
 int qd_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int levels, float* alpha, float* beta,
                    uint8_t* level_idx, const float* mean, int clamp, float max_element, int stochastic,

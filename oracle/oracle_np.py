@@ -113,7 +113,9 @@ def uniform_quantize(x, s, bucket=None, max_element=False, subtract_mean=False, 
 
 def uniform_quantize_stochastic(x, s, rand, bucket=None, max_element=False, subtract_mean=False, mean=None):
     """Stochastic-rounding variant given the uniform [0,1) draws `rand` (bucket layout).
-    ref: quant_functions.py:174-187."""
+    ref: quant_functions.py:174-187.  `rand <= prob` (:187): an element exactly on a level (prob == 0) moves one level up
+    when its draw is 0.0 -- the bucket's maximum to level s, one past the top, and q follows.  `lev` is the level INDEX both
+    libraries store in their optional uint8 output (include/qd_hip.h): floor + increment, saturated at s - 1, NaN as 0."""
     sd = scale_down(x, bucket, max_element, subtract_mean, mean)
     sm1 = F32(s - 1)
     prob = (sm1 * sd['u']).astype(F32)                            # :179
@@ -121,35 +123,54 @@ def uniform_quantize_stochastic(x, s, rand, bucket=None, max_element=False, subt
     fl = np.floor(t).astype(F32)                                  # :181
     prob = (prob - fl).astype(F32)                                # :182
     w = (fl / sm1).astype(F32)                                    # :183
-    inc = ((np.asarray(rand, dtype=F32).reshape(w.shape) <= prob).astype(F32) * F32(1.0) / sm1).astype(F32)
+    up = np.asarray(rand, dtype=F32).reshape(w.shape) <= prob
+    inc = (up.astype(F32) * F32(1.0) / sm1).astype(F32)
     w = (w + inc).astype(F32)                                     # :187
     q = inv_scale_down(w, sd['alpha'], sd['beta'], sd['mean'], sd['n'], sd['shape'])
+    lev = np.minimum(fl + up.astype(F32), sm1)                    # (NaN stays NaN through np.minimum)
     out = dict(sd)
-    out.update(q=q)
+    out.update(q=q, lev=np.where(np.isnan(lev), F32(0.0), lev).astype(np.int32), up=up)
     return out
 
 
-def philox4x32_7_uniform(seed, n):
-    """The uniform [0,1) draw of every element index 0..n-1 under the in-kernel generator of the HIP path
-    (quantized_distillation_amd/csrc/qd_common.h: philox_uniform4) -- Philox4x32 with 7 rounds, counter =
-    (element >> 2, 0x51ed270b, 0x2545f491), key = the 64-bit seed, component = element & 3, 24 mantissa bits.
-    This restates OUR generator (the reference draws torch.rand on the host, quant_functions.py:185-186, which
-    no device generator can reproduce); it lets the stochastic branch be checked bit for bit on every kernel
-    path instead of only statistically."""
+def philox4x32(counter, key, rounds):
+    """Philox4x32 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) with `rounds` rounds:
+    counter = four 32-bit words, key = two 32-bit words (scalars or arrays that broadcast against each other).  Returns the four output words as
+    uint64 arrays.  A round multiplies c0 by M0 and c2 by M1 and returns (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0); the key
+    is bumped by the Weyl constants AFTER each round (so the first round sees the key itself).  At 10 rounds this is
+    Random123's philox4x32_10, pinned by its published known-answer vectors in tests/test_stochastic_host.py."""
     M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
     mask = np.uint64(0xFFFFFFFF)
-    blocks = np.arange((n + 3) // 4, dtype=np.uint64)
-    c0, c1 = blocks & mask, blocks >> np.uint64(32)
-    c2 = np.full_like(blocks, 0x51ed270b)
-    c3 = np.full_like(blocks, 0x2545f491)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for _ in range(7):
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.atleast_1d(np.asarray(c, dtype=np.uint64)) & mask for c in counter])
+    k0, k1 = (np.asarray(k, dtype=np.uint64) & mask for k in key)   # scalars, or arrays that broadcast against the counter
+    for _ in range(rounds):
         p0, p1 = M0 * c0, M1 * c2                                   # 32 x 32 -> 64-bit products
         hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & mask, p1 >> np.uint64(32), p1 & mask
         c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
         k0 = (k0 + np.uint64(0x9E3779B9)) & mask
         k1 = (k1 + np.uint64(0xBB67AE85)) & mask
-    words = np.stack([c0, c1, c2, c3], axis=1).reshape(-1)[:n]
+    return c0, c1, c2, c3
+
+
+def philox4x32_7_words(seed, n, first=0):
+    """The 32-bit word behind the draw of every element index first..first + n - 1 (first % 4 == 0): Philox4x32 with 7
+    rounds, counter = (element >> 2 as two words, 0x51ed270b, 0x2545f491), key = the 64-bit seed, word = element & 3."""
+    assert first % 4 == 0
+    blocks = np.arange(first // 4, first // 4 + (n + 3) // 4, dtype=np.uint64)
+    words = philox4x32((blocks & np.uint64(0xFFFFFFFF), blocks >> np.uint64(32), 0x51ed270b, 0x2545f491),
+                       (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF), 7)
+    return np.stack(words, axis=1).reshape(-1)[:n]
+
+
+def philox4x32_7_uniform(seed, n):
+    """The uniform [0,1) draw of every element index 0..n-1 under the in-kernel generator of the HIP path
+    (quantized_distillation_amd/csrc/qd_common.h: philox_uniform4) -- Philox4x32 with 7 rounds, counter =
+    (element >> 2, 0x51ed270b, 0x2545f491), key = the 64-bit seed, component = element & 3, and the draw is the word's
+    TOP 24 bits times 2^-24: a multiple of 2^-24 in [0, 1 - 2^-24], exactly 0.0 once in 2^24 draws.
+    This restates OUR generator (the reference draws torch.rand on the host, quant_functions.py:185-186, which
+    no device generator can reproduce); it lets the stochastic branch be checked bit for bit on every kernel
+    path instead of only statistically."""
+    words = philox4x32_7_words(seed, n)
     return ((words >> np.uint64(8)).astype(np.float32) * F32(1.0 / 16777216.0)).astype(F32)
 
 

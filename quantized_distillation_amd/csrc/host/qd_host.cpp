@@ -209,7 +209,9 @@ QD_CLONES static void span_inv(const float* u, float* y, int64_t lo, int64_t hi,
     }
 }
 
-// stochastic variant (:174-187): floor + Bernoulli(frac)
+// stochastic variant (:174-187): floor + Bernoulli(frac).  "rnd <= p" as the reference (:187): an element exactly on a level
+// (p == 0) moves one level up when its draw is exactly 0.0, the bucket's maximum to level s, one past the top.  q follows the
+// reference there; the level index saturates at s - 1 (csrc/qd_common.h: stochastic_level, include/qd_hip.h).
 inline float qdq_stochastic(float v, float a, float b, float sm1, float mean, float rnd, float& level) {
     float u = v - b;
     u = u / a;
@@ -218,7 +220,8 @@ inline float qdq_stochastic(float v, float a, float b, float sm1, float mean, fl
     float p = t - l;
     float w = l / sm1;
     float inc = (rnd <= p) ? (1.0f / sm1) : 0.0f;
-    level = l + ((rnd <= p) ? 1.0f : 0.0f);
+    const float lv = l + ((rnd <= p) ? 1.0f : 0.0f);
+    level = lv > sm1 ? sm1 : lv;
     w = w + inc;
     float y = w * a;
     y = y + b;

@@ -328,7 +328,18 @@ __device__ __forceinline__ void philox_uniform4(uint64_t seed, uint64_t block, f
 #pragma unroll
     for (int i = 0; i < 4; ++i) out[i] = (float)(c[i] >> 8) * (1.0f / 16777216.0f);
 }
-// stochastic variant (quant_functions.py:174-187): floor + Bernoulli(frac)
+// stochastic variant (quant_functions.py:174-187): floor + Bernoulli(frac).  The reference adds 1 / (s - 1) where
+// rand <= probabilities (:187) -- "<=", not "<" -- with probabilities = t - floor(t) in [0, 1) and rand in [0, 1).  So an
+// element that sits exactly ON level l (p == 0: the bucket's minimum and maximum always do) still moves up to level l + 1
+// when its draw is exactly 0.0, once in 2^24 draws here; for the bucket's maximum that is level s, ONE PAST THE TOP:
+// q = ((s - 1) / (s - 1) + 1 / (s - 1)) alpha + beta.  The value q follows the reference there.  The level INDEX (the
+// optional uint8 side output) keeps the range the header documents, [0, s - 1]: it saturates at s - 1 (with s = 256 the
+// index 256 would not fit its byte and would spill into the neighbour's in the packed stores).  A NaN level stays NaN
+// through the comparison and is stored as 0.  tests/stochastic_cases.py pins all of it.
+__device__ __forceinline__ float stochastic_level(float l, bool up, float sm1) {
+    const float lv = l + (up ? 1.0f : 0.0f);
+    return lv > sm1 ? sm1 : lv;
+}
 template <bool FAST = false>
 __device__ __forceinline__ float qdq_stochastic(float v, float a, float b, float sm1, float mean, float rnd,
                                                 float& level, float ry = 0.0f) {
@@ -339,7 +350,7 @@ __device__ __forceinline__ float qdq_stochastic(float v, float a, float b, float
     float p = t - l;
     float w = l / sm1;
     float inc = (rnd <= p) ? (1.0f / sm1) : 0.0f;
-    level = l + ((rnd <= p) ? 1.0f : 0.0f);
+    level = stochastic_level(l, rnd <= p, sm1);
     w = w + inc;
     float y = w * a;
     y = y + b;
@@ -359,7 +370,7 @@ __device__ __forceinline__ float qdq_stochastic_tab(float v, float a, float b, f
     const int src = (int)(threadIdx.x & 48) + (int)l;
     float w = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(tab)));
     float inc = (rnd <= p) ? (1.0f / sm1) : 0.0f;
-    level = l + ((rnd <= p) ? 1.0f : 0.0f);
+    level = stochastic_level(l, rnd <= p, sm1);
     w = w + inc;
     float y = w * a;
     y = y + b;

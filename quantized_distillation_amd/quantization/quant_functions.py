@@ -27,7 +27,16 @@ def next_stochastic_seed(peek=False, host=False):
     (ref: :185-186); here the draws come from an in-kernel counter-based generator keyed by this
     seed and the element index.  The seed is derived from the CURRENT DEVICE's default generator
     seed (so torch.manual_seed / torch.cuda.manual_seed control it) and a per-process call counter
-    (so successive calls draw different numbers)."""
+    (so successive calls draw different numbers): call k after the process started uses base + k, so two successive
+    launches differ by 1 in the low key word of the generator.
+
+    The seed reaches the kernel as a by-value launch argument.  A launch captured into a hipGraph would therefore replay
+    the SAME draws at every replay -- every training step rounding every weight the same way -- so a stochastic call on a
+    device tensor while its stream is being captured raises instead of recording one."""
+    if not host and not peek and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('stochastic_rounding=True during stream capture: the seed of the in-kernel generator is a '
+                           'launch argument, so every replay of the captured graph would repeat the same draws. '
+                           'Make the stochastic call outside the captured region.')
     calls = _STOCHASTIC_CALLS[0] + 1
     if not peek:
         _STOCHASTIC_CALLS[0] = calls
