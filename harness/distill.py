@@ -32,7 +32,8 @@ class DistillTrainer(object):
     def __init__(self, student, teacher, device, num_bits=4, bucket_size=256, lr=1e-3, momentum=0.9,
                  weight_decay=2.2e-4, nesterov=True, quantize_first_and_last_layer=True, mode='multi',
                  backprop_quantization_style='none', grad_chunks=1, overlap_allreduce=False, loss_fn=None,
-                 clip_norm=None, teacher_stream=False, estimate_quant_grad_every=1, quantize_from_first_step=True):
+                 clip_norm=None, teacher_stream=False, estimate_quant_grad_every=1, quantize_from_first_step=True,
+                 stochastic_rounding=False, max_element=False):
         """backprop_quantization_style: 'none' (pure STE), 'truncated' (clamp the quantized masters to
         [-1, 1] before quantizing and zero the gradient where |w| > 1) or 'complicated' (bucket-aware
         STE, K7) -- ref: conv_forward_model.py:213-229,240-266; anything else raises as the reference
@@ -40,7 +41,10 @@ class DistillTrainer(object):
         between run on the full-precision weights (ref: :286,:320-323).  quantize_from_first_step:
         the CNN loop's counter starts at 1, so the first batch is quantized (ref: :198); the seq2seq
         loop's starts at 0, so its first batch is NOT (ref: translation_models/model.py:184,243) --
-        pass False for that loop."""
+        pass False for that loop.  stochastic_rounding / max_element: handed to every quantization as the
+        seq2seq loop hands them (ref: translation_models/model.py:162,200-209); mode='multi' keeps the
+        seed of the stochastic draws in device memory, so capture() records a step that rounds anew
+        at every replay."""
         style = 'none' if backprop_quantization_style is None else str(backprop_quantization_style).lower()
         if style not in STYLES:
             raise ValueError('The specified backprop_quantization_style not recognized')      # ref: :228-229
@@ -60,6 +64,8 @@ class DistillTrainer(object):
             p.requires_grad_(False)
         self.s = 2 ** num_bits                                   # ref: conv_forward_model.py:209-211
         self.bucket_size = bucket_size
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.max_element = max_element
         self.mode = mode
         self.style = style
         self.every = max(1, int(estimate_quant_grad_every))
@@ -98,7 +104,8 @@ class DistillTrainer(object):
                 p.data = shadows[i] if self.quantized[i] else self.masters[i]
             qi = [i for i in range(n) if self.quantized[i]]
             self.mt = MultiTensorQuantizer([self.masters[i] for i in qi], self.s, bucket_size,
-                                           outputs=[shadows[i] for i in qi])
+                                           outputs=[shadows[i] for i in qi], stochastic_rounding=self.stochastic_rounding,
+                                           max_element=max_element, seed_on_device=self.stochastic_rounding)
             if style == 'complicated':                           # K7 over all quantized masters, in place on the flat gradient
                 self.mt_ste = MultiTensorSTE([self.masters[i] for i in qi], [grads[i] for i in qi], self.s, bucket_size)
         else:
@@ -128,7 +135,9 @@ class DistillTrainer(object):
         else:                                                    # the reference's loop shape, :235-247
             for i, p in enumerate(self.params):
                 if self.quantized[i]:
-                    p.data = quantization.uniformQuantization(self.masters[i], self.s, bucket_size=self.bucket_size)[0]
+                    p.data = quantization.uniformQuantization(self.masters[i], self.s, bucket_size=self.bucket_size,
+                                                              stochastic_rounding=self.stochastic_rounding,
+                                                              max_element=self.max_element)[0]
         self._quantized_step = True
 
     def skip_quantize(self):

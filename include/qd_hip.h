@@ -223,6 +223,31 @@ int64_t qd_multi_global_plan(QdTensorDesc* host_table, int ntensors);
 int qd_multi_uniform_global_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int levels,
                                 float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-tensor K1 / K1g with the options the reference's loops hand to every per-parameter call
+ * (translation_models/model.py:162,200-209: stochasticRounding, maxElementAllowedForQuantization).  Tables and tile counts
+ * come from qd_multi_plan / qd_multi_global_plan as above; mean subtraction is not offered (qd_mean_f32 is an
+ * order-dependent sum of its own launch).
+ *   Contract: with stochastic == 0 && clamp == 0 the result equals qd_multi_uniform_f32 / qd_multi_uniform_global_f32; in
+ *   every configuration tensor i of the table equals
+ *       qd_uniform_f32(x_i, q_i, n_i, bucket, levels, NULL, NULL, NULL, NULL, clamp, max_element, stochastic, seed0 + i, ...)
+ *   bit for bit (bucket = 0 for the global form, whose alpha_beta rows are that call's alpha and beta).
+ *   Seed rule: tensor i draws with seed0 + i modulo 2^64 -- i is the POSITION in the table, tensors without elements
+ *   included -- and its element e takes word e & 3 of Philox block e >> 2, as qd_uniform_f32 documents.  seed0 is `seed`
+ *   when seed_cell == NULL, else *seed_cell: one 8-byte-aligned word of DEVICE memory that the kernel reads (once per wave)
+ *   and never writes.
+ *   Capture: a by-value seed is frozen into a captured launch, which then replays the same draws.  A launch that reads
+ *   seed_cell draws whatever the cell holds when the replay runs: advance the cell by ntensors on the same stream after the
+ *   launch (inside the captured region) and every replay rounds anew, replay r using seed0 + r * ntensors + i.
+ *   Errors: clamp != 0 with max_element not a positive number, or seed_cell not 8-byte aligned: QD_ERR_INVALID_ARGUMENT;
+ *   the global form's workspace as above (QD_ERR_WORKSPACE_TOO_SMALL, nothing written); total_tiles == 0 returns 0
+ *   without a launch.  stochastic == 0 ignores seed and seed_cell. */
+int qd_multi_uniform_opt_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, int levels,
+                             int clamp, float max_element, int stochastic, uint64_t seed, const uint64_t* seed_cell,
+                             void* stream);
+int qd_multi_uniform_global_opt_f32(const QdTensorDesc* table, int ntensors, int64_t total_tiles, int levels,
+                                    int clamp, float max_element, int stochastic, uint64_t seed, const uint64_t* seed_cell,
+                                    float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Multi-tensor K7: the 'complicated' straight-through backward of every quantized parameter of a model in ONE launch (the
  * per-step loop `quantizeFunctions[idx].backward(p.grad.data)`, cnn_models/conv_forward_model.py:253-266).  `table` is a
  * DEVICE array of descriptors; each tensor is bucketed independently with the same bucket / levels / tie_mode and its result

@@ -13,6 +13,7 @@ per-tensor descriptors {pointers, numel, work prefix} once (_DeviceTable) and ru
 per step (include/qd_hip.h); the results are bit-identical to the per-tensor calls.
 """
 import ctypes
+import numbers
 
 import torch
 
@@ -87,24 +88,50 @@ class _DeviceTable(object):
 
 
 class MultiTensorQuantizer(_DeviceTable):
-    """uniformQuantization(t, s, bucket_size)[0] of every tensor, written to outputs[i], in one launch (qd_multi_uniform_f32;
-    bucket_size=None: three, qd_multi_uniform_global_f32, and `alpha_beta` holds every tensor's (alpha, beta))."""
+    """uniformQuantization(t, s, bucket_size=bucket_size, stochastic_rounding=..., max_element=...)[0] of every tensor, written
+    to outputs[i], in one launch (qd_multi_uniform_f32; bucket_size=None: three, qd_multi_uniform_global_f32, and `alpha_beta`
+    holds every tensor's (alpha, beta)).  With an option set the launch is qd_multi_uniform_opt_f32 /
+    qd_multi_uniform_global_opt_f32; with none it is what it always was.
+
+    stochastic_rounding: tensor i is rounded with seed0 + i, what the i-th call of the per-tensor loop draws
+    (quant_functions.reserve_stochastic_seeds).  By default seed0 is a launch argument: quantize(seed=...) or the process
+    counter, kept as `last_seed`; such a launch cannot be captured into a hipGraph (it would replay its draws).
+    seed_on_device=True keeps seed0 in `seed_cell`, one int64 device word that reseed() writes and every quantize() advances
+    by n_tensors on the launch's stream: nothing on the host is consulted, so the call can be captured and each replay
+    draws anew -- launch r after a reseed uses seed0 + r * n_tensors + i (int64 wrap-around gives the bits of uint64).
+    subtract_mean is not offered: call uniformQuantization per tensor for it."""
     _DESC = _lib.QdTensorDesc
     _WATCH = ('inputs', 'outputs')
 
-    def __init__(self, tensors, s, bucket_size, outputs=None):
+    def __init__(self, tensors, s, bucket_size, outputs=None, stochastic_rounding=False, max_element=False,
+                 subtract_mean=False, seed_on_device=False):
         if bucket_size is not None and (not isinstance(bucket_size, int) or bucket_size <= 0):
             raise ValueError('bucket_size must be a positive integer or None')
         if int(s) != s or s < 2:
             raise ValueError('s must be an integer >= 2')
+        if max_element is not False and (max_element is True or not isinstance(max_element, numbers.Number)):
+            raise ValueError('maxElementAllowed must be a number')                  # as ScalingFunction, ref: :31-33
+        if subtract_mean:
+            raise NotImplementedError('MultiTensorQuantizer does not subtract the mean (a per-tensor, order-dependent sum): '
+                                      'call quantization.uniformQuantization(t, s, subtract_mean=True, ...) per tensor')
+        if seed_on_device and not stochastic_rounding:
+            raise ValueError('seed_on_device=True needs stochastic_rounding=True')
         self.s = int(s)
         self.bucket_size = bucket_size
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.max_element = max_element
+        self.seed_on_device = bool(seed_on_device)
+        self.last_seed = None
+        self.seed_cell = None
         if outputs is None:
             (self.inputs,) = self._adopt(tensors=tensors)
             self.outputs = [torch.empty_like(t) for t in self.inputs]
         else:
             self.inputs, self.outputs = self._adopt(tensors=tensors, outputs=outputs)
         self._plan()
+        if self.seed_on_device:
+            self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.reseed()
 
     def _columns(self):
         return ('x', self.inputs), ('q', self.outputs)
@@ -128,9 +155,49 @@ class MultiTensorQuantizer(_DeviceTable):
         return _lib.load().qd_multi_uniform_f32(self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s,
                                                 _lib.stream_ptr(self.device))
 
-    def quantize(self, check_pointers=True):
-        """Quantize all tensors (one launch).  Returns the list of output tensors."""
-        return self._launch(self._call, self.outputs, check_pointers)
+    def _call_opt(self, seed):
+        clamp, me = (0, 0.0) if self.max_element is False else (1, float(self.max_element))
+        cell = self.seed_cell.data_ptr() if self.seed_on_device else None
+        if self.bucket_size is None:
+            return _lib.load().qd_multi_uniform_global_opt_f32(
+                self._table.data_ptr(), self.n_tensors, self._tiles, self.s, clamp, me, int(self.stochastic_rounding), seed,
+                cell, self.alpha_beta.data_ptr(), self._scratch.data_ptr(), self._scratch.numel() * 4,
+                _lib.stream_ptr(self.device))
+        return _lib.load().qd_multi_uniform_opt_f32(
+            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s, clamp, me,
+            int(self.stochastic_rounding), seed, cell, _lib.stream_ptr(self.device))
+
+    def reseed(self, seed0=None):
+        """seed_on_device: write the device seed word; the next quantize() rounds tensor i with seed0 + i.  Default: the next
+        n_tensors seeds of the process counter (quant_functions.reserve_stochastic_seeds).  Not inside a captured region."""
+        if not self.seed_on_device:
+            raise ValueError('reseed() needs seed_on_device=True')
+        if seed0 is None:
+            from .quantization.quant_functions import reserve_stochastic_seeds
+            seed0 = reserve_stochastic_seeds(self.n_tensors)
+        seed0 = int(seed0) & 0xFFFFFFFFFFFFFFFF
+        self.seed_cell.fill_(seed0 - (1 << 64) if seed0 >= (1 << 63) else seed0)      # the same 64 bits as int64
+        return seed0
+
+    def quantize(self, check_pointers=True, seed=None):
+        """Quantize all tensors (one launch).  Returns the list of output tensors.  seed: the by-value seed0 of a stochastic
+        launch (default: the next n_tensors seeds of the process counter); kept as `last_seed`."""
+        if seed is not None and (not self.stochastic_rounding or self.seed_on_device):
+            raise ValueError('seed= is for stochastic_rounding=True with the seed passed by value (seed_on_device=False)')
+        if not self.stochastic_rounding and self.max_element is False:
+            return self._launch(self._call, self.outputs, check_pointers)
+        seed0 = 0
+        if self.stochastic_rounding and not self.seed_on_device:
+            from .quantization.quant_functions import next_stochastic_seed, reserve_stochastic_seeds
+            if seed is None:
+                seed = reserve_stochastic_seeds(self.n_tensors)       # raises during stream capture
+            elif torch.cuda.is_current_stream_capturing():
+                next_stochastic_seed()                                # the same RuntimeError: a by-value seed would be replayed
+            self.last_seed = seed0 = int(seed) & 0xFFFFFFFFFFFFFFFF
+        out = self._launch(lambda: self._call_opt(seed0), self.outputs, check_pointers)
+        if self.seed_on_device:
+            self.seed_cell.add_(self.n_tensors)        # on the launch's stream: the next launch, or replay, draws anew
+        return out
 
 
 class MultiTensorDiffQuant(_DeviceTable):

@@ -44,6 +44,18 @@ def next_stochastic_seed(peek=False, host=False):
     return (base * 0x9E3779B97F4A7C15 + calls) & 0xFFFFFFFFFFFFFFFF
 
 
+def reserve_stochastic_seeds(count, host=False):
+    """The seeds of the next `count` stochastic-rounding launches at once, for a launch that rounds `count` tensors: returns
+    the seed the next call of next_stochastic_seed() would get and advances the process counter by `count`, so tensor i of
+    the launch (seed + i modulo 2^64) uses exactly what the i-th call of the per-tensor loop would have drawn.  Raises the
+    same RuntimeError during stream capture."""
+    if isinstance(count, bool) or not isinstance(count, numbers.Integral) or count < 1:
+        raise ValueError('count must be an integer >= 1')
+    first = next_stochastic_seed(host=host)
+    _STOCHASTIC_CALLS[0] += int(count) - 1
+    return first
+
+
 def _bucket_arg(bucket_size):
     return 0 if bucket_size is None else int(bucket_size)
 
