@@ -33,7 +33,8 @@ class DiffQuantTrainer(object):
         """num_points: one count for every tensor.  With assign_bits_automatically the counts are spread over
         the tensors by the 2-norm of their gradients under the plain cross-entropy loss on `estimate_batches`
         (the reference uses 5 mini-batches; ref: :424-448, help_functions.py:97-138), so tensors end up with
-        different numbers of points."""
+        different numbers of points.  mode='multi' takes bucket_size=None or any positive int and up to 256 points per
+        tensor after the redistribution (ValueError above that)."""
         self.device = device
         self.teacher = model.to(device).eval()                       # ref: :496 modelToQuantize.eval()
         for p in self.teacher.parameters():
@@ -50,6 +51,9 @@ class DiffQuantTrainer(object):
         if assign_bits_automatically:
             self.counts = self._assign_counts(estimate_batches, self.counts)
         self.k = max(self.counts)
+        if mode == 'multi' and self.k > 256:
+            raise ValueError("mode='multi' carries uint8 point indices: at most 256 points per tensor, the counts ask for %d "
+                             "(use mode='per_tensor')" % self.k)
         scaling = quantization.ScalingFunction('linear', False, False, bucket_size, False)     # ref: :421
         # all points live in ONE [ntensors, k] tensor: one optimizer state, one all-reduce.  Rows of tensors
         # with fewer than k points are padded with +inf: a point at +inf is never the nearest one (its

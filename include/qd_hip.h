@@ -83,7 +83,9 @@ extern "C" {
  * added, 4-byte data alignment; 3 = qd_scale_digitize_histogram_f32 added, QdDiffQuantDesc.first_row (partial rows of
  * qd_multi_point_grad_f32 per tensor size instead of 4 B + 1 for every tensor); qd_huffman_encode / qd_huffman_decode_f32
  * and qd_multi_ste_plan / qd_multi_ste_backward_f32 were added later without a bump (new symbols only, nothing existing
- * changed meaning).
+ * changed meaning).  qd_multi_dq_plan / qd_multi_nearest_f32 / qd_multi_point_grad_f32 take bucket == 0, buckets that are
+ * no power of two and k up to 256, also without a bump: arguments that were rejected are now accepted; nothing existing
+ * changed meaning.
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -290,8 +292,13 @@ int qd_inv_scale_abs_f32(const float* u, const float* sign, float* y, int64_t n,
  *     p_quantized.data = quantizationFunctions[i].forward(None, points[i].data)   (conv_forward_model.py:532)
  *     points[i].grad.data = quantizationFunctions[i].backward(p.grad.data)[1]     (conv_forward_model.py:545)
  * for ALL tensors in one launch each.  Arithmetic = qd_nearest_point_f32(prescaled, MIDPOINT) with
- * uint8 indices and qd_point_grad_f32.  k <= 64; bucket a power of two; `points` is one device
- * array [ntensors][k] (so the optimizer updates a single tensor); grad_points likewise. */
+ * uint8 indices and qd_point_grad_f32.  1 <= k <= 256 (the index is a byte; a NaN u takes k - 1); bucket == 0 means "no
+ * buckets" as everywhere in this header (one alpha[0] / beta[0] per tensor), any bucket > 0 is taken, and a tensor of
+ * n <= bucket elements is one bucket.  `points` is one device array [ntensors][k] (so the optimizer updates a single
+ * tensor); grad_points likewise.  Tuned: buckets 64 / 128 / 256 with k <= 64 and, forward only, bucket == 0.  Functional,
+ * not tuned: k > 64 (the backward sweep then runs one wave per block, its lane-private bins [k][64] floats of LDS = 64 KB at
+ * k = 256) and buckets that are no power of two (forward: a 16-lane group per bucket, element-wise; backward: alpha looked up
+ * per element, a float4 can straddle a bucket end). */
 typedef struct QdDiffQuantDesc {
     const float* u;       /* scaled weights, resident [n]                                  */
     float* q;             /* quantized weights out [n]                                     */
@@ -300,18 +307,21 @@ typedef struct QdDiffQuantDesc {
     const float* beta;    /* [num_buckets]                                                 */
     const float* grad;    /* dLoss/dq [n] (backward only)                                  */
     int64_t n;
-    int64_t first_tile;   /* filled by qd_multi_dq_plan: prefix of 4-bucket tiles (forward) */
+    int64_t first_tile;   /* filled by qd_multi_dq_plan: prefix of forward tiles (4 buckets; bucket == 0: 1024 elements) */
     int64_t first_block;  /* filled by qd_multi_dq_plan: prefix of FULL 1024-element gradient tiles (backward) */
     int64_t first_row;    /* filled by qd_multi_dq_plan: prefix of the backward sweep's partial rows (ABI 3)  */
 } QdDiffQuantDesc;
-/* Host helper: fills first_tile / first_block / first_row, returns the total of forward tiles, writes `total_blocks` = the
+/* Host helper: fills first_tile / first_block / first_row, returns the total of forward tiles (bucket > 0: ceil(buckets / 4)
+ * per tensor; bucket == 0: ceil(n / 1024) per tensor; an empty tensor has none), writes `total_blocks` = the
  * number of partial rows of the backward sweep: min(full 1024-element gradient tiles, 2048) + 1 per tensor (the 2048 waves of
  * the main grid stride over the ONE sequence of all tensors' full tiles and write one row per tensor they visit; one more
- * wave per tensor takes the n mod 1024 elements left).  Pass it to qd_multi_point_grad_f32 unchanged. */
+ * wave per tensor takes the n mod 1024 elements left); first_block, first_row and total_blocks do not depend on the bucket.
+ * Pass it to qd_multi_point_grad_f32 unchanged. */
 int64_t qd_multi_dq_plan(QdDiffQuantDesc* host_table, int ntensors, int64_t bucket, int64_t* total_blocks_out);
 int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles, int64_t bucket,
                          const float* points, int k, void* stream);
-/* workspace: at least total_blocks * k floats */
+/* workspace: at least total_blocks * k floats, contents need no initialisation -- at k = 256 that is 1 KiB per partial row,
+ * at most (2048 + 1) KiB ~ 2 MiB per tensor (WRN-16-22, 60 tensors: 21001 rows = 21.5 MB) */
 int qd_multi_point_grad_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k,
                             float* grad_points, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -15,7 +15,47 @@ using namespace qd;
 
 namespace {
 
-constexpr int kMaxK = 64;
+constexpr int kMaxK = 256;                             // the index is a uint8
+
+// this tensor's points and fp32 midpoints (quant_functions.py:533) into the wave's LDS slot;
+// LDS operations of one wave complete in order, the barriers only stop compiler reordering
+__device__ __forceinline__ void load_point_tables(float* pts, float* mid, const float* points, int k, int lane) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int j = lane; j < k; j += 64) pts[j] = points[j];             // one pass while k <= 64
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int j = lane; j + 1 < k; j += 64) {
+        float df = pts[j + 1] - pts[j];
+        df = df / 2.0f;
+        mid[j] = pts[j] + df;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one element: the count over the midpoints (a NaN orders last, as in qd_nearest_point_f32), then p alpha, + beta, + 0.0f
+// as three separately rounded operations
+__device__ __forceinline__ int nearest1(const float* pts, const float* mid, int k, float u, float a, float b, float& q) {
+    int id = count_before<true>(mid, k - 1, u);
+    id = u != u ? k - 1 : id;
+    float y = pts[id] * a;
+    y = y + b;
+    q = y + 0.0f;
+    return id;
+}
+
+// a float4 of one bucket: the quantized values and the four indices packed for one 4-byte store
+__device__ __forceinline__ uint32_t nearest4(const float* pts, const float* mid, int k, const f4& v, float a, float b, f4& r) {
+    float q0, q1, q2, q3;
+    const uint32_t i0 = (uint32_t)nearest1(pts, mid, k, v.x, a, b, q0);
+    const uint32_t i1 = (uint32_t)nearest1(pts, mid, k, v.y, a, b, q1);
+    const uint32_t i2 = (uint32_t)nearest1(pts, mid, k, v.z, a, b, q2);
+    const uint32_t i3 = (uint32_t)nearest1(pts, mid, k, v.w, a, b, q3);
+    r.x = q0; r.y = q1; r.z = q2; r.w = q3;
+    return i0 | (i1 << 8) | (i2 << 16) | (i3 << 24);
+}
 
 // forward: a tile = 4 buckets of one tensor = one wave iteration; a DPP row owns a bucket
 template <int ROW>
@@ -30,19 +70,7 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
     for (int64_t t = wave; t < total_tiles; t += nwaves) {
         const int ti = owner_of(table, ntensors, t);                   // wave-uniform
         const QdDiffQuantDesc d = table[ti];
-        // this tensor's points and fp32 midpoints (quant_functions.py:533) into the wave's LDS slot;
-        // LDS operations of one wave complete in order, the barriers only stop compiler reordering
-        __builtin_amdgcn_wave_barrier();
-        if (lane < k) s_pts[w][lane] = points[(int64_t)ti * k + lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane + 1 < k) {
-            float df = s_pts[w][lane + 1] - s_pts[w][lane];
-            df = df / 2.0f;
-            s_mid[w][lane] = s_pts[w][lane] + df;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        load_point_tables(s_pts[w], s_mid[w], points + (int64_t)ti * k, k, lane);
         const int64_t row = d.n < bucket ? d.n : bucket;
         const int64_t nb = (d.n + row - 1) / row;
         const int64_t bkt = (t - d.first_tile) * 4 + sub;
@@ -61,29 +89,63 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
             for (int j = 0; j < V; ++j) v[j] = ldg_nt(src + j * 16);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                int id[4];
                 f4 r;
-#define QD_ONE(c, n_)                                                         \
-                {                                                             \
-                    id[n_] = count_before<true>(s_mid[w], k - 1, v[j].c);     \
-                    id[n_] = v[j].c != v[j].c ? k - 1 : id[n_];               /* a NaN orders last, as in qd_nearest_point_f32 */ \
-                    float y = s_pts[w][id[n_]] * a;                           \
-                    y = y + b;                                                \
-                    r.c = y + 0.0f;                                           \
-                }
-                QD_ONE(x, 0) QD_ONE(y, 1) QD_ONE(z, 2) QD_ONE(w, 3)
-#undef QD_ONE
+                const uint32_t pk = nearest4(s_pts[w], s_mid[w], k, v[j], a, b, r);
                 stg_nt(r, dst + j * 16);
-                const uint32_t pk = (uint32_t)id[0] | ((uint32_t)id[1] << 8) | ((uint32_t)id[2] << 16) | ((uint32_t)id[3] << 24);
                 stg(pk, (uint32_t*)(d.idx + lo + ((int64_t)(j * 16 + l) << 2)));
             }
         } else {
             for (int64_t i = lo + l; i < hi; i += 16) {
-                const float ui = d.u[i];
-                const int id = ui != ui ? k - 1 : count_before<true>(s_mid[w], k - 1, ui);
-                float y = s_pts[w][id] * a;
-                y = y + b;
-                d.q[i] = y + 0.0f;
+                float q;
+                const int id = nearest1(s_pts[w], s_mid[w], k, d.u[i], a, b, q);
+                d.q[i] = q;
+                d.idx[i] = (uint8_t)id;
+            }
+        }
+    }
+}
+
+// forward without buckets (bucket == 0): a tile = kFlatTile consecutive elements of one tensor = one wave iteration, all under
+// the tensor's one (alpha[0], beta[0]).  A full tile of aligned pointers: four float4 loads of u per lane up front, per float4
+// one float4 store of q and one packed store of the four indices; a tensor's last partial tile, and tensors whose u / q are
+// not 16-byte or whose idx is not 4-byte aligned, go element by element.
+constexpr int kFlatTile = 1024;
+
+__global__ __launch_bounds__(256) void k_multi_nearest_flat(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                            int64_t total_tiles, const float* points, int k) {
+    __shared__ float s_pts[4][kMaxK];
+    __shared__ float s_mid[4][kMaxK];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t wave = uniform_wave_index();
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);                   // wave-uniform
+        const QdDiffQuantDesc d = table[ti];
+        load_point_tables(s_pts[w], s_mid[w], points + (int64_t)ti * k, k, lane);
+        const int64_t lo = (t - d.first_tile) * kFlatTile;
+        const int64_t hi = lo + kFlatTile < d.n ? lo + kFlatTile : d.n;
+        const float a = ldg(d.alpha), b = ldg(d.beta);
+        const bool fast = (hi - lo) == kFlatTile &&
+                          (((((uintptr_t)d.u) | ((uintptr_t)d.q)) & 15) == 0) && ((((uintptr_t)d.idx) & 3) == 0);
+        if (fast) {
+            const f4* src = (const f4*)(d.u + lo) + lane;
+            f4* dst = (f4*)(d.q + lo) + lane;
+            uint32_t* ix = (uint32_t*)(d.idx + lo) + lane;
+            f4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ldg_nt(src + j * 64);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f4 r;
+                const uint32_t pk = nearest4(s_pts[w], s_mid[w], k, v[j], a, b, r);
+                stg_nt(r, dst + j * 64);
+                stg(pk, ix + j * 64);
+            }
+        } else {
+            for (int64_t i = lo + lane; i < hi; i += 64) {
+                float q;
+                const int id = nearest1(s_pts[w], s_mid[w], k, d.u[i], a, b, q);
+                d.q[i] = q;
                 d.idx[i] = (uint8_t)id;
             }
         }
@@ -111,8 +173,8 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
 // k = 64) and the fold reads them front to back.  Which rows exist is a function of the table alone, so nothing needs zeroing.
 // Fixed tile -> wave assignment, fixed fold order: deterministic.
 constexpr int kGradTile = 1024;
-constexpr int kGradBlocks = 512;                       // the main grid: 2048 waves x 4 independent 1 KiB streams, the shape that
-constexpr int64_t kGradWaves = 4 * kGradBlocks;        // measured best for qd_point_grad_f32; blocks beyond the last tile return at once
+constexpr int64_t kGradWaves = 2048;                   // the main grid: 2048 waves x 4 independent 1 KiB streams, the shape that
+                                                       // measured best for qd_point_grad_f32; waves beyond the last tile return at once
 
 // T is not an argument of the entry point (the host holds no copy of the device table): the last tensor's prefix + its tiles
 __device__ __forceinline__ int64_t total_grad_tiles(const QdDiffQuantDesc* table, int ntensors) {
@@ -131,15 +193,20 @@ __device__ __forceinline__ int owner_of_tile(const QdDiffQuantDesc* table, int n
     return __builtin_amdgcn_readfirstlane(cnt - 1);
 }
 
-// KR > 0: k <= KR bins in registers (compare-select-add); KR == 0: lane-private LDS columns [k][256]
-template <int KR>
-__global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc* __restrict__ table, int ntensors,
-                                                          int64_t bucket, int row_shift, int k, float* part /* [rows][k] */) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];        // KR == 0: [k][256]
+// KR > 0: k <= KR bins in registers (compare-select-add); KR == 0: lane-private LDS columns [k][64 WPB].
+// WPB: waves per block -- 4 while the columns of k <= 64 bins fit 64 KB of LDS, 1 above that ([256][64] floats = 64 KB); the
+// tile -> wave -> row assignment is that of the 2048 waves whatever a block holds of them, so the fold does not change.
+// DIV: the bucket is not a power of two -- the alpha of element e is alpha[e / bucket], looked up per element (a float4 can
+// straddle a bucket end); otherwise alpha[e >> row_shift], one per float4.  Functional, not tuned.
+template <int KR, int WPB, bool DIV>
+__global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                               int64_t bucket, int row_shift, int k, float* part /* [rows][k] */) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];        // KR == 0: [k][64 WPB]
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    constexpr int B = kGradBlocks;
+    constexpr int C = 64 * WPB;                                        // columns = lanes of a block
     constexpr int64_t W = kGradWaves;
+    constexpr int B = (int)(W / WPB);                                  // blocks of the main grid
     float acc[KR > 0 ? KR : 1];
     float* col = lds + threadIdx.x;                                    // this lane's column; a wave owns columns 64 w ... 64 w + 63
     auto clear = [&]() {
@@ -147,7 +214,7 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
 #pragma unroll
             for (int j = 0; j < (KR > 0 ? KR : 1); ++j) acc[j] = 0.0f;
         } else {
-            for (int j = 0; j < k; ++j) col[j * 256] = 0.0f;
+            for (int j = 0; j < k; ++j) col[j * C] = 0.0f;
         }
     };
     auto add = [&](int id, float m) {
@@ -155,7 +222,7 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
 #pragma unroll
             for (int j = 0; j < (KR > 0 ? KR : 1); ++j) acc[j] += (id == j) ? m : 0.0f;
         } else {
-            col[id * 256] += m;                                        // private column: plain LDS read-add-write
+            col[id * C] += m;                                          // private column: plain LDS read-add-write
         }
     };
     auto flush = [&](const QdDiffQuantDesc& dd, int64_t r) {           // this wave's sums for tensor dd -> its row for wave r (W: the extra wave), bins cleared
@@ -181,26 +248,48 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
             // of this wave (rotated start: bank-conflict free) in a fixed order.
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            if (lane < k) {
-                const float* base = lds + lane * 256 + 64 * w;
+            auto fold_bin = [&](int j) {
+                const float* base = lds + j * C + 64 * w;
                 float s0 = 0.0f, s1 = 0.0f;
                 for (int c = 0; c < 64; c += 2) { s0 += base[(c + lane) & 63]; s1 += base[(c + 1 + lane) & 63]; }
-                row[lane] = s0 + s1;
+                row[j] = s0 + s1;
+            };
+            if (WPB == 4) {                                             // k <= 64: one pass, as one statement (as a loop it costs 25 VGPRs)
+                if (lane < k) fold_bin(lane);
+            } else {
+#pragma unroll 1
+                for (int j = lane; j < k; j += 64) fold_bin(j);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
         clear();
     };
+    auto bucket_of = [&](int64_t e) { return DIV ? e / bucket : e >> row_shift; };
+    // the alphas of the `cnt` (<= 4) elements from e on.  DIV: a bucket that is no power of two holds at least 3 elements, so
+    // at most one bucket end lies inside e ... e + 3
+    auto alpha4 = [&](const QdDiffQuantDesc& d, bool single, int64_t e, int64_t cnt, float (&a)[4]) {
+        if (!DIV) {
+            a[0] = a[1] = a[2] = a[3] = cnt > 0 ? ldg(d.alpha + (single ? 0 : bucket_of(e))) : 0.0f;
+        } else {
+            const int64_t b0 = single ? 0 : e / bucket;
+            const int64_t r = e - b0 * bucket;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int step = r + j >= bucket ? 1 : 0;              // r + j < bucket + 3 <= 2 bucket
+                a[j] = cnt > j ? ldg(d.alpha + (single ? 0 : b0 + step)) : 0.0f;
+            }
+        }
+    };
     auto scalar_span = [&](const QdDiffQuantDesc& d, int64_t lo, int64_t hi) {        // element by element (a view at an odd offset)
         const bool single = d.n <= bucket;
         for (int64_t e = lo + lane; e < hi; e += 64)
-            add((int)d.idx[e], d.grad[e] * d.alpha[single ? 0 : (e >> row_shift)]);
+            add((int)d.idx[e], d.grad[e] * d.alpha[single ? 0 : bucket_of(e)]);
     };
 
     if ((int)blockIdx.x >= B) {
         // ---- the extra waves: what is left of tensor ti after its full tiles
-        const int ti = ((int)blockIdx.x - B) * 4 + w;
+        const int ti = ((int)blockIdx.x - B) * WPB + w;
         if (ti >= ntensors) return;
         const QdDiffQuantDesc d = table[ti];
         const int64_t rem = d.n % kGradTile;
@@ -221,7 +310,8 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
                 const int64_t lu = left - 256 * u;
                 const float* gs = (const float*)(g4 + 64 * u);
                 const uint8_t* is = (const uint8_t*)(i4 + 64 * u);
-                const float al = lu > 0 ? ldg(d.alpha + (single ? 0 : ((e0 + 256 * u + 4 * lane) >> row_shift))) : 0.0f;
+                float al[4];
+                alpha4(d, single, e0 + 256 * u + 4 * lane, lu, al);
                 f4 gq = {0.0f, 0.0f, 0.0f, 0.0f};
                 uint32_t pq = 0;
                 if (lu >= 4) {
@@ -232,8 +322,8 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
                     if (lu > 1) { gq.y = gs[1]; pq |= (uint32_t)is[1] << 8; }
                     if (lu > 2) { gq.z = gs[2]; pq |= (uint32_t)is[2] << 16; }
                 }
-                gv[u].x = lu > 0 ? gq.x * al : 0.0f; gv[u].y = lu > 1 ? gq.y * al : 0.0f;     // one fp32 multiply each, quant_functions.py:495
-                gv[u].z = lu > 2 ? gq.z * al : 0.0f; gv[u].w = lu > 3 ? gq.w * al : 0.0f;
+                gv[u].x = lu > 0 ? gq.x * al[0] : 0.0f; gv[u].y = lu > 1 ? gq.y * al[1] : 0.0f;     // one fp32 multiply each, quant_functions.py:495
+                gv[u].z = lu > 2 ? gq.z * al[2] : 0.0f; gv[u].w = lu > 3 ? gq.w * al[3] : 0.0f;
                 pk[u] = pq;
             }
 #pragma unroll
@@ -252,7 +342,7 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
 
     // ---- the main grid: full tiles only
     const int64_t T = total_grad_tiles(table, ntensors);
-    const int64_t g = (int64_t)blockIdx.x * 4 + w;                     // a block's waves take four adjacent tiles
+    const int64_t g = (int64_t)blockIdx.x * WPB + w;                   // a block's waves take adjacent tiles
     if (g >= T) return;
     int ti = owner_of_tile(table, ntensors, g, lane);                  // once per wave
     clear();
@@ -272,20 +362,20 @@ __global__ __launch_bounds__(256) void k_multi_point_grad(const QdDiffQuantDesc*
         if (aligned) {                                                  // four (gradient float4, four indices, alpha) loads up front
             const f4* g4 = (const f4*)(d.grad + e0) + lane;
             const uint32_t* i4 = (const uint32_t*)(d.idx + e0) + lane;
-            f4 gv[4]; uint32_t pk[4]; float a[4];
+            f4 gv[4]; uint32_t pk[4]; float a[4][4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 gv[u] = ldg_nt(g4 + 64 * u);
                 pk[u] = ldg_nt(i4 + 64 * u);
-                a[u] = ldg(d.alpha + (d.n <= bucket ? 0 : ((e0 + 256 * u + 4 * lane) >> row_shift)));      // n <= bucket: one alpha
+                alpha4(d, d.n <= bucket, e0 + 256 * u + 4 * lane, 4, a[u]);                                 // n <= bucket: one alpha
             }
             __builtin_amdgcn_sched_barrier(0);                          // keep the loads together (not sunk to their uses)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                add(pk[u] & 255, gv[u].x * a[u]);                       // one fp32 multiply each, quant_functions.py:495
-                add((pk[u] >> 8) & 255, gv[u].y * a[u]);
-                add((pk[u] >> 16) & 255, gv[u].z * a[u]);
-                add(pk[u] >> 24, gv[u].w * a[u]);
+                add(pk[u] & 255, gv[u].x * a[u][0]);                    // one fp32 multiply each, quant_functions.py:495
+                add((pk[u] >> 8) & 255, gv[u].y * a[u][1]);
+                add((pk[u] >> 16) & 255, gv[u].z * a[u][2]);
+                add(pk[u] >> 24, gv[u].w * a[u][3]);
             }
         } else {
             scalar_span(d, e0, e0 + kGradTile);
@@ -329,17 +419,17 @@ __global__ __launch_bounds__(256) void k_multi_point_grad_final(const QdDiffQuan
 extern "C" {
 
 int64_t qd_multi_dq_plan(QdDiffQuantDesc* host_table, int ntensors, int64_t bucket, int64_t* total_blocks_out) {
-    if (!host_table || ntensors <= 0 || bucket <= 0 || !total_blocks_out) return -1;
+    if (!host_table || ntensors <= 0 || bucket < 0 || !total_blocks_out) return -1;
     int64_t tiles = 0, gtiles = 0, rows = 0;
     for (int i = 0; i < ntensors; ++i) {
         const int64_t n = host_table[i].n;
-        const int64_t row = n < bucket ? (n > 0 ? n : 1) : bucket;
+        const int64_t row = bucket == 0 || n < bucket ? (n > 0 ? n : 1) : bucket;
         const int64_t nb = n > 0 ? (n + row - 1) / row : 0;
         host_table[i].first_tile = tiles;
         host_table[i].first_block = gtiles;              // prefix of FULL 1024-element gradient tiles (k_multi_point_grad)
         host_table[i].first_row = rows;                  // prefix of partial rows: min(full tiles, 2048) + 1 per tensor
         const int64_t full = n > 0 ? n / kGradTile : 0;
-        tiles += (nb + 3) / 4;
+        tiles += bucket == 0 ? (n > 0 ? (n + kFlatTile - 1) / kFlatTile : 0) : (nb + 3) / 4;     // k_multi_nearest_flat / k_multi_nearest
         gtiles += full;
         rows += (full < kGradWaves ? full : kGradWaves) + 1;
     }
@@ -349,13 +439,14 @@ int64_t qd_multi_dq_plan(QdDiffQuantDesc* host_table, int ntensors, int64_t buck
 
 int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles, int64_t bucket,
                          const float* points, int k, void* stream) {
-    if (!table || ntensors <= 0 || total_tiles < 0 || bucket <= 0 || !points || k < 1 || k > kMaxK)
+    if (!table || ntensors <= 0 || total_tiles < 0 || bucket < 0 || !points || k < 1 || k > kMaxK)
         return QD_ERR_INVALID_ARGUMENT;
     if (total_tiles == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     int64_t b = (total_tiles + 3) / 4;
     const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
-    if (bucket == 256) hipLaunchKernelGGL((k_multi_nearest<256>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);
+    if (bucket == 0) hipLaunchKernelGGL(k_multi_nearest_flat, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, points, k);
+    else if (bucket == 256) hipLaunchKernelGGL((k_multi_nearest<256>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);
     else if (bucket == 128) hipLaunchKernelGGL((k_multi_nearest<128>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);
     else if (bucket == 64) hipLaunchKernelGGL((k_multi_nearest<64>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);
     else hipLaunchKernelGGL((k_multi_nearest<0>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);
@@ -364,25 +455,34 @@ int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t tot
 
 int qd_multi_point_grad_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k,
                             float* grad_points, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!table || ntensors <= 0 || total_blocks <= 0 || bucket <= 0 || (bucket & (bucket - 1)) || k < 1 || k > kMaxK ||
-        !grad_points)
+    if (!table || ntensors <= 0 || total_blocks <= 0 || bucket < 0 || k < 1 || k > kMaxK || !grad_points)
         return QD_ERR_INVALID_ARGUMENT;
     // total_blocks is what qd_multi_dq_plan wrote: between 1 and 2048 + 1 partial rows per tensor
     if (total_blocks < ntensors || total_blocks > (kGradWaves + 1) * (int64_t)ntensors) return QD_ERR_INVALID_ARGUMENT;
     if (!workspace || (((uintptr_t)workspace) & 15) || workspace_bytes < (size_t)total_blocks * k * sizeof(float))
         return QD_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
+    const bool div = (bucket & (bucket - 1)) != 0;                     // alpha[e / bucket] per element instead of alpha[e >> row_shift]
+    const int64_t kb = bucket == 0 ? INT64_MAX : bucket;               // no buckets: every tensor is "n <= bucket", one alpha
     int row_shift = 0;
-    while (((int64_t)1 << row_shift) < bucket) ++row_shift;
+    while (row_shift < 62 && ((int64_t)1 << row_shift) < kb) ++row_shift;
     float* part = (float*)workspace;
-    // grid: the 512 blocks of the sweep over the full tiles (a wave beyond the last tile returns at once) + one wave per
-    // tensor for what is left after them
-    const unsigned grid = (unsigned)(kGradBlocks + (ntensors + 3) / 4);
-    if (k <= 4)
-        hipLaunchKernelGGL((k_multi_point_grad<4>), dim3(grid), dim3(256), 0, st, table, ntensors, bucket, row_shift, k, part);
-    else
-        hipLaunchKernelGGL((k_multi_point_grad<0>), dim3(grid), dim3(256), (size_t)k * 256 * sizeof(float), st, table, ntensors,
-                           bucket, row_shift, k, part);
+    // grid: the blocks of the sweep over the full tiles, 2048 waves in all (a wave beyond the last tile returns at once) + one
+    // wave per tensor for what is left after them
+    auto launch = [&](auto kernel, int wpb, size_t lds) {
+        const unsigned grid = (unsigned)(kGradWaves / wpb + (ntensors + wpb - 1) / wpb);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * wpb), lds, st, table, ntensors, kb, row_shift, k, part);
+    };
+    if (k <= 4) {
+        if (div) launch(k_multi_point_grad<4, 4, true>, 4, 0);
+        else launch(k_multi_point_grad<4, 4, false>, 4, 0);
+    } else if (k <= 64) {
+        if (div) launch(k_multi_point_grad<0, 4, true>, 4, (size_t)k * 256 * sizeof(float));
+        else launch(k_multi_point_grad<0, 4, false>, 4, (size_t)k * 256 * sizeof(float));
+    } else {                                                           // [k][64] columns: 64 KB at k = 256
+        if (div) launch(k_multi_point_grad<0, 1, true>, 1, (size_t)k * 64 * sizeof(float));
+        else launch(k_multi_point_grad<0, 1, false>, 1, (size_t)k * 64 * sizeof(float));
+    }
     hipLaunchKernelGGL(k_multi_point_grad_final, dim3((unsigned)(ntensors * k)), dim3(256), 0, st, table, ntensors, k, part,
                        grad_points);
     return (int)hipGetLastError();

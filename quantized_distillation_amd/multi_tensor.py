@@ -211,16 +211,21 @@ class MultiTensorDiffQuant(_DeviceTable):
         forward():  points -> quantized weights written straight into `outputs[i]` (+ uint8 indices)
         backward(): gradients `grads[i]` -> grad of the points, [ntensors, k]
     Results are bit-identical (forward) / equal to rounding (backward) to the per-tensor calls.
+
+    bucket_size: None (no buckets: one alpha / beta per tensor) or any positive int, as the per-tensor functions take them;
+    num_points: 1 ... 256 (the index is a uint8).  Powers of two with at most 64 points are the tuned path; other bucket
+    sizes and more points run the same launches through untuned instantiations.
     """
     _DESC = _lib.QdDiffQuantDesc
     _WATCH = ('outputs', 'grads')
 
     def __init__(self, tensors, outputs, grads, num_points, bucket_size):
         from .quantization.quant_functions import ScalingFunction
-        if not isinstance(bucket_size, int) or bucket_size <= 0 or bucket_size & (bucket_size - 1):
-            raise ValueError('the multi-tensor diff-quant path needs a power-of-two bucket_size')
-        if not 1 <= num_points <= 64:
-            raise ValueError('the multi-tensor diff-quant path supports 1..64 points per tensor')
+        if bucket_size is not None and (type(bucket_size) is not int or bucket_size <= 0):      # as ScalingFunction (bool refused)
+            raise ValueError('Bucket size must be an integer and strictly positive. '
+                             'Pass None if you want to avoid using buckets')
+        if type(num_points) is not int or not 1 <= num_points <= 256:
+            raise ValueError('the multi-tensor diff-quant path supports 1..256 points per tensor (uint8 indices)')
         self.k, self.bucket_size = int(num_points), bucket_size
         # OWNING references: the device table below holds raw pointers into these tensors, so they are kept
         # alive here for the lifetime of the object.  A caller that rebinds `p.grad` (zero_grad(set_to_none=True))
@@ -241,7 +246,7 @@ class MultiTensorDiffQuant(_DeviceTable):
 
     def _plan_table(self, host, n):
         rows = ctypes.c_int64(0)
-        tiles = int(_lib.load().qd_multi_dq_plan(host, n, self.bucket_size, ctypes.byref(rows)))
+        tiles = int(_lib.load().qd_multi_dq_plan(host, n, self.bucket_size or 0, ctypes.byref(rows)))
         if tiles < 0:
             raise RuntimeError('qd_multi_dq_plan failed')
         self._blocks = int(rows.value)             # partial rows of the gradient sweep
@@ -260,7 +265,7 @@ class MultiTensorDiffQuant(_DeviceTable):
         if points.shape != (self.n_tensors, self.k) or not points.is_contiguous():
             raise ValueError('points must be a contiguous [ntensors, k] tensor')
         return self._launch(lambda: _lib.load().qd_multi_nearest_f32(
-            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, points.data_ptr(), self.k,
+            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size or 0, points.data_ptr(), self.k,
             _lib.stream_ptr(self.device)), self.outputs)
 
     def backward(self, out=None):
@@ -268,7 +273,7 @@ class MultiTensorDiffQuant(_DeviceTable):
         if out is None:
             out = torch.empty(self.n_tensors, self.k, dtype=torch.float32, device=self.device)
         self._launch(lambda: _lib.load().qd_multi_point_grad_f32(
-            self._table.data_ptr(), self.n_tensors, self._blocks, self.bucket_size, self.k, out.data_ptr(),
+            self._table.data_ptr(), self.n_tensors, self._blocks, self.bucket_size or 0, self.k, out.data_ptr(),
             self._scratch.data_ptr(), self._scratch.numel() * 4, _lib.stream_ptr(self.device)))
         return out
 
