@@ -16,6 +16,8 @@ The straight-through estimator is the wiring itself: gradients are taken at the 
 and applied to the full-precision masters.  mode='per_tensor' keeps the reference's structure
 (per-parameter API calls + save/restore) for comparison.
 """
+import numbers
+
 import torch
 
 import quantization
@@ -44,7 +46,9 @@ class DistillTrainer(object):
         pass False for that loop.  stochastic_rounding / max_element: handed to every quantization as the
         seq2seq loop hands them (ref: translation_models/model.py:162,200-209); mode='multi' keeps the
         seed of the stochastic draws in device memory, so capture() records a step that rounds anew
-        at every replay."""
+        at every replay.  num_bits: one width for the whole model, or a sequence with one entry per parameter of the
+        student (per-layer widths, e.g. 8 bits first and last, 4 or 2 in between); the entries of parameters that are not
+        quantized are ignored.  Both modes and every style take it."""
         style = 'none' if backprop_quantization_style is None else str(backprop_quantization_style).lower()
         if style not in STYLES:
             raise ValueError('The specified backprop_quantization_style not recognized')      # ref: :228-229
@@ -53,6 +57,11 @@ class DistillTrainer(object):
                                       ' Not hard to modify though')                           # ref: quant_functions.py:332-334
         if mode not in ('multi', 'per_tensor'):
             raise ValueError("mode must be 'multi' or 'per_tensor'")
+        per_param = not isinstance(num_bits, numbers.Real)
+        if per_param:
+            num_bits = list(num_bits)
+            if any(isinstance(b, bool) or not isinstance(b, numbers.Real) or int(b) != b or b < 1 for b in num_bits):
+                raise ValueError('num_bits must be a positive integer, or a sequence of them with one entry per parameter')
         self.device = device
         # optional: the teacher forward (needs neither the quantized weights nor the student) on its own HIP
         # stream beside quantize + student forward, joined before the KD loss.  Measured on the CIFAR step:
@@ -62,7 +71,7 @@ class DistillTrainer(object):
         self.teacher = teacher.to(device).eval()
         for p in self.teacher.parameters():
             p.requires_grad_(False)
-        self.s = 2 ** num_bits                                   # ref: conv_forward_model.py:209-211
+        self.s = [2 ** int(b) for b in num_bits] if per_param else 2 ** num_bits      # ref: conv_forward_model.py:209-211
         self.bucket_size = bucket_size
         self.stochastic_rounding = bool(stochastic_rounding)
         self.max_element = max_element
@@ -74,6 +83,9 @@ class DistillTrainer(object):
         params = list(self.student.parameters())
         self.params = params
         n = len(params)
+        if per_param and len(self.s) != n:
+            raise ValueError('num_bits has %d entries for %d parameters: need one per parameter' % (len(self.s), n))
+        self.s_of = self.s if per_param else [self.s] * n        # the level count of parameter i
         self.quantized = [not (not quantize_first_and_last_layer and (i == 0 or i == n - 1)) for i in range(n)]
         layout = FlatLayout([p.shape for p in params])
         self.layout = layout
@@ -103,11 +115,12 @@ class DistillTrainer(object):
                 # the model computes on the shadow (or straight on the master when not quantized)
                 p.data = shadows[i] if self.quantized[i] else self.masters[i]
             qi = [i for i in range(n) if self.quantized[i]]
-            self.mt = MultiTensorQuantizer([self.masters[i] for i in qi], self.s, bucket_size,
+            s_q = [self.s_of[i] for i in qi] if per_param else self.s
+            self.mt = MultiTensorQuantizer([self.masters[i] for i in qi], s_q, bucket_size,
                                            outputs=[shadows[i] for i in qi], stochastic_rounding=self.stochastic_rounding,
                                            max_element=max_element, seed_on_device=self.stochastic_rounding)
             if style == 'complicated':                           # K7 over all quantized masters, in place on the flat gradient
-                self.mt_ste = MultiTensorSTE([self.masters[i] for i in qi], [grads[i] for i in qi], self.s, bucket_size)
+                self.mt_ste = MultiTensorSTE([self.masters[i] for i in qi], [grads[i] for i in qi], s_q, bucket_size)
         else:
             for i, p in enumerate(params):
                 p.data = self.masters[i]
@@ -135,7 +148,7 @@ class DistillTrainer(object):
         else:                                                    # the reference's loop shape, :235-247
             for i, p in enumerate(self.params):
                 if self.quantized[i]:
-                    p.data = quantization.uniformQuantization(self.masters[i], self.s, bucket_size=self.bucket_size,
+                    p.data = quantization.uniformQuantization(self.masters[i], self.s_of[i], bucket_size=self.bucket_size,
                                                               stochastic_rounding=self.stochastic_rounding,
                                                               max_element=self.max_element)[0]
         self._quantized_step = True
@@ -167,7 +180,7 @@ class DistillTrainer(object):
             grads = self.layout.views(self.flat_grad)
             for i in range(len(self.params)):
                 if self.quantized[i]:
-                    ste.ste_bucket_backward(self.masters[i], grads[i], self.bucket_size, self.s, out=grads[i])
+                    ste.ste_bucket_backward(self.masters[i], grads[i], self.bucket_size, self.s_of[i], out=grads[i])
 
     def forward_backward(self, *batch):
         self.flat_grad.zero_()

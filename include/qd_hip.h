@@ -85,7 +85,8 @@ extern "C" {
  * and qd_multi_ste_plan / qd_multi_ste_backward_f32 were added later without a bump (new symbols only, nothing existing
  * changed meaning).  qd_multi_dq_plan / qd_multi_nearest_f32 / qd_multi_point_grad_f32 take bucket == 0, buckets that are
  * no power of two and k up to 256, also without a bump: arguments that were rejected are now accepted; nothing existing
- * changed meaning.
+ * changed meaning.  qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 / qd_multi_ste_backward_levels_f32 (a level
+ * count per tensor) are new symbols, likewise without a bump.
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -250,6 +251,27 @@ int qd_multi_uniform_global_opt_f32(const QdTensorDesc* table, int ntensors, int
                                     int clamp, float max_element, int stochastic, uint64_t seed, const uint64_t* seed_cell,
                                     float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-tensor K1 / K1g with a level count PER TENSOR (per-layer bit widths, e.g. 8 bits for the first and the last layer and
+ * 4 or 2 in between: what the per-tensor loop does when it calls uniformQuantization(t_i, s_i, ...)).  Tables and tile counts
+ * come from qd_multi_plan / qd_multi_global_plan as above: neither depends on the level count.
+ *   levels: a DEVICE array of ntensors int32 values, 4-byte aligned; entry i belongs to position i of the table, tensors
+ *   without elements included.  The kernels read it (one scalar load per tile) and never write it.
+ *   Contract: tensor i of the table equals
+ *       qd_uniform_f32(x_i, q_i, n_i, bucket, levels[i], NULL, NULL, NULL, NULL, clamp, max_element, stochastic, seed0 + i, ...)
+ *   bit for bit (bucket = 0 for the global form, whose alpha_beta row i is that call's alpha and beta; the row of a tensor
+ *   without elements is (1, +inf)).  The seed rule, the capture rule, the workspace, aliasing (q may alias x) and
+ *   total_tiles == 0 (returns 0 without a launch) are those of qd_multi_uniform_opt_f32 / qd_multi_uniform_global_opt_f32.
+ *   Errors: levels == NULL or not 4-byte aligned, and everything the _opt entry points refuse: QD_ERR_INVALID_ARGUMENT; the
+ *   global form's workspace: QD_ERR_WORKSPACE_TOO_SMALL, nothing written.
+ *   The library cannot look into device memory without a synchronisation, so the VALUES of levels are the caller's: an entry
+ *   < 2 gives wrong values in that tensor's output (q_i, and nothing else: no other tensor, no other memory). */
+int qd_multi_uniform_levels_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                int64_t bucket, int clamp, float max_element, int stochastic, uint64_t seed,
+                                const uint64_t* seed_cell, void* stream);
+int qd_multi_uniform_global_levels_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                       int clamp, float max_element, int stochastic, uint64_t seed, const uint64_t* seed_cell,
+                                       float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Multi-tensor K7: the 'complicated' straight-through backward of every quantized parameter of a model in ONE launch (the
  * per-step loop `quantizeFunctions[idx].backward(p.grad.data)`, cnn_models/conv_forward_model.py:253-266).  `table` is a
  * DEVICE array of descriptors; each tensor is bucketed independently with the same bucket / levels / tie_mode and its result
@@ -271,6 +293,14 @@ typedef struct QdSteDesc {
 int qd_multi_ste_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out);
 int qd_multi_ste_backward_f32(const QdSteDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, int levels,
                               int tie_mode, void* stream);
+/* The same with a level count per tensor: `levels` as qd_multi_uniform_levels_f32 documents it (a DEVICE array of ntensors
+ * int32, 4-byte aligned, entry i for position i of the table, empty tensors included; NULL or misaligned:
+ * QD_ERR_INVALID_ARGUMENT).  Table and tile count come from qd_multi_ste_plan, which does not depend on the level count.
+ * Tensor i equals qd_ste_bucket_backward_f32(x_i, g_i, out_i, n_i, bucket, levels[i], tie_mode, ...) bit for bit, every bucket
+ * summed in the order that call sums it; out may alias g; total_tiles == 0 returns 0 without a launch.  An entry < 2 gives
+ * wrong values in out_i and touches nothing else. */
+int qd_multi_ste_backward_levels_f32(const QdSteDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                     int64_t bucket, int tie_mode, void* stream);
 
 /* ---- 'absmax' / 'absnorm' scaling (type_scaling of ScalingFunction, quant_functions.py:109-127,144-146).
  * PARITY UNPINNED: the reference code for these two types raises on every torch version, so these

@@ -18,6 +18,7 @@ qd_huffman_encode / qd_huffman_decode_f32 (csrc/qd_huffman.hip, csrc/host/qd_hos
 import collections
 import ctypes
 import math
+import numbers
 import struct
 import zlib
 
@@ -148,8 +149,9 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
     """Quantize `tensors` (an ordered name -> tensor mapping, or an nn.Module's named_parameters()) and write them in
     Huffman-coded form; returns a report (section bytes, file bytes, mean code length, coding, reference_size_mb).
 
-    Exactly one of `s` (uniform, 2 <= s <= 256 levels) or `points` (non-uniform: one sorted list of at most 256 points per
-    quantized tensor, or one list for all) is given.  quantize_first_last=False stores the first and the last tensor as raw
+    Exactly one of `s` (uniform, 2 <= s <= 256 levels: one count for all, or a sequence with one entry per QUANTIZED tensor
+    in the order of `tensors` -- with quantize_first_last=False the first and the last tensor have no entry) or `points`
+    (non-uniform: one sorted list of at most 256 points per quantized tensor, or one list for all) is given.  quantize_first_last=False stores the first and the last tensor as raw
     fp32 (the reference's quantizeFirstLastLayer).  `buffers` (e.g. BN running statistics) are stored as raw fp32.  The
     quantizer options are the ones the training loops save with: linear scaling, deterministic rounding, no mean subtraction,
     no max_element; any other raises ValueError."""
@@ -160,8 +162,15 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
         raise ValueError('give exactly one of s (uniform) or points (non-uniform)')
     if bucket_size is not None and (isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0):
         raise ValueError('bucket_size must be a positive int or None')
-    if s is not None and (isinstance(s, bool) or int(s) != s or not 2 <= s <= 256):
-        raise ValueError('s must be an integer in 2 .. 256')
+    s_list = None                       # the entries of a sequence s
+    if s is not None:
+        scalar = isinstance(s, numbers.Real)
+        if not scalar and (isinstance(s, (str, bytes)) or not hasattr(s, '__iter__')):
+            raise ValueError('s must be an integer in 2 .. 256, or a sequence of them with one entry per quantized tensor')
+        s_list = None if scalar else list(s)
+        for v in ([s] if scalar else s_list):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or int(v) != v or not 2 <= v <= 256:
+                raise ValueError('s must be an integer in 2 .. 256, or a sequence of them with one entry per quantized tensor')
     params = _named(tensors, 'tensors')
     bufs = _named(buffers, 'buffers')
     names = [n for n, _ in params] + [n for n, _ in bufs]
@@ -177,6 +186,10 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
     quant = [i for i in range(T) if quantize_first_last or i not in (0, T - 1)]
     mode = 0 if s is not None else 1
     pts = _point_list(points, len(quant)) if mode else None
+    if s_list is not None and len(s_list) != len(quant):
+        raise ValueError('s has %d entries for %d quantized tensors: need one per quantized tensor' % (len(s_list), len(quant)))
+    if mode == 0:
+        s = [int(v) for v in s_list] if s_list is not None else [int(s)] * len(quant)
     if dev.type == 'cuda':
         with torch.cuda.device(dev):
             return _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev)
@@ -190,7 +203,7 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
     qx = [params[i][1].contiguous().view(-1) for i in quant]
     ns = [x.numel() for x in qx]
     nbs = [_nbuckets(n, bucket_size) for n in ns]
-    levels = [int(s)] * len(quant) if mode == 0 else [p.numel() for p in pts]
+    levels = s if mode == 0 else [p.numel() for p in pts]         # mode 0: s is the list of level counts, one per quantized tensor
     sym_off, o = [], 0
     for n in ns:
         sym_off.append(o)

@@ -10,6 +10,8 @@
 //               maxElementAllowedForQuantization.  Siblings, not flags: the plain kernels above keep their code.  Tensor i of the
 //               table draws with seed0 + i, seed0 a launch argument or one device word (a captured launch then draws anew
 //               at every replay, once the cell has been advanced on the stream).
+//   levels      qd_multi_uniform_levels_f32, qd_multi_uniform_global_levels_f32   k_multi_uniform_lv, k_mg_apply_lv: the forms with
+//               options again, with a level count per tensor from a device array beside the table ("8 bits first and last").
 #include "qd_transform.h"      // bucket_row16, KParams, Prep for k_multi_uniform; launch geometry
 #include "qd_multi.h"
 
@@ -363,6 +365,166 @@ __global__ __launch_bounds__(256) void k_mg_apply_opt(const QdTensorDesc* __rest
     }
 }
 
+// ---- a level count per tensor: k_multi_uniform_opt / k_mg_apply_opt with sm1 taken from the tensor's row of a device table ----
+// levels[ti] is read with the descriptor, from the index owner_of returns: wave-uniform, a scalar load.  What the kernels above
+// derive from sm1 once per wave -- use_tab and tab = (float)(lane & 15) / sm1, the same correctly rounded division -- is derived
+// here whenever the wave moves on to another tensor (a scalar branch; the tiles of one tensor that a wave takes in a row share
+// it).  An entry < 2 gives sm1 <= 0: wrong values in that tensor's output and nothing else (sm1 is never an address; the table
+// lookup of qdq_tab is a cross-lane read).  Siblings again: the kernels above keep their code.
+template <int ROW, int STOCH>
+__global__ __launch_bounds__(256) void k_multi_uniform_lv(const QdTensorDesc* __restrict__ table, const int32_t* __restrict__ levels,
+                                                          int ntensors, int64_t total_tiles, int64_t bucket, float me, uint64_t seed,
+                                                          const uint64_t* __restrict__ seed_cell) {
+    const int lane = threadIdx.x & 63;
+    const int sub = lane >> 4, l = lane & 15;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t seed0 = STOCH ? first_seed(seed, seed_cell) : 0;
+    Prep pp;
+    pp.mean = 0.0f;
+    pp.me = me;
+    int cur = -1;                                   // the tensor sm1 / use_tab / tab below belong to
+    float sm1 = 1.0f, tab = 0.0f;
+    bool use_tab = false;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdTensorDesc d = table[ti];
+        if (ti != cur) {
+            cur = ti;
+            sm1 = (float)(levels[ti] - 1);
+            use_tab = sm1 <= 15.0f;
+            tab = (float)(lane & 15) / sm1;
+        }
+        const uint64_t seed_t = seed0 + (uint64_t)ti;
+        KParams p;
+        p.x = d.x; p.out = d.q; p.n = d.n;
+        p.row = d.n < bucket ? d.n : bucket;
+        p.nb = (d.n + p.row - 1) / p.row;
+        p.alpha = nullptr; p.beta = nullptr; p.mean = nullptr; p.me = me; p.sm1 = sm1; p.lev8 = nullptr;
+        p.idx = nullptr; p.idx_bytes = 0; p.pts = nullptr; p.k = 0; p.assign_mode = 0; p.prescaled = 0;
+        p.stochastic = STOCH; p.seed = seed_t; p.nvec = 0;
+        const int64_t bkt = (t - d.first_tile) * 4 + sub;
+        if (bkt >= p.nb) continue;
+        const int64_t lo = bkt * p.row;
+        const int64_t hi = lo + p.row < p.n ? lo + p.row : p.n;
+        const bool fast = ROW > 0 && (hi - lo) == ROW && p.row == ROW &&
+                          (((((uintptr_t)d.x) | ((uintptr_t)d.q)) & 15) == 0);
+        if (fast) {
+            constexpr int V = ROW > 0 ? ROW / 64 : 1;
+            const f4* src = (const f4*)(p.x + lo) + l;
+            f4 v[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = ldg_nt(src + j * 16);   // masters: read once
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = prep4(v[j], pp);        // the clamp comes before the bucket's min / max
+            float mn = pmin4(v[0]), mx = pmax4(v[0]);      // NaN-propagating
+#pragma unroll
+            for (int j = 1; j < V; ++j) { mn = pmin(mn, pmin4(v[j])); mx = pmax(mx, pmax4(v[j])); }
+            mn = row16_min(mn); mx = row16_max(mx);
+            float a, b, lev;
+            alpha_beta(mn, mx, a, b);
+            f4* dst = (f4*)(p.out + lo) + l;
+            const uint64_t blk0 = (uint64_t)(lo >> 2) + (uint64_t)l;      // Philox block of this lane's first float4
+            // rows of the wave that took this branch: all in the proven range -> bucket-invariant division (qd_common.h)
+            const bool fdiv = !__any(!fastdiv_ok(a));
+            auto body = [&](auto fast_c) {
+                constexpr bool FAST = decltype(fast_c)::value;
+                const float y = FAST ? 1.0f / a : 0.0f;
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    float rnd[4] = {0.f, 0.f, 0.f, 0.f};
+                    if (STOCH) philox_uniform4(seed_t, blk0 + (uint64_t)(j * 16), rnd);
+                    f4 r;
+                    if (STOCH && use_tab) {                // <= 16 levels: a DPP row is active as a whole here
+                        r.x = qdq_stochastic_tab<FAST>(v[j].x, a, b, sm1, 0.0f, rnd[0], lev, tab, y);
+                        r.y = qdq_stochastic_tab<FAST>(v[j].y, a, b, sm1, 0.0f, rnd[1], lev, tab, y);
+                        r.z = qdq_stochastic_tab<FAST>(v[j].z, a, b, sm1, 0.0f, rnd[2], lev, tab, y);
+                        r.w = qdq_stochastic_tab<FAST>(v[j].w, a, b, sm1, 0.0f, rnd[3], lev, tab, y);
+                    } else if (STOCH) {
+                        r.x = qdq_stochastic<FAST>(v[j].x, a, b, sm1, 0.0f, rnd[0], lev, y);
+                        r.y = qdq_stochastic<FAST>(v[j].y, a, b, sm1, 0.0f, rnd[1], lev, y);
+                        r.z = qdq_stochastic<FAST>(v[j].z, a, b, sm1, 0.0f, rnd[2], lev, y);
+                        r.w = qdq_stochastic<FAST>(v[j].w, a, b, sm1, 0.0f, rnd[3], lev, y);
+                    } else if (use_tab) {
+                        r.x = qdq_tab<FAST>(v[j].x, a, b, sm1, 0.0f, lev, tab, y);
+                        r.y = qdq_tab<FAST>(v[j].y, a, b, sm1, 0.0f, lev, tab, y);
+                        r.z = qdq_tab<FAST>(v[j].z, a, b, sm1, 0.0f, lev, tab, y);
+                        r.w = qdq_tab<FAST>(v[j].w, a, b, sm1, 0.0f, lev, tab, y);
+                    } else {
+                        r.x = qdq<FAST>(v[j].x, a, b, sm1, 0.0f, lev, y);
+                        r.y = qdq<FAST>(v[j].y, a, b, sm1, 0.0f, lev, y);
+                        r.z = qdq<FAST>(v[j].z, a, b, sm1, 0.0f, lev, y);
+                        r.w = qdq<FAST>(v[j].w, a, b, sm1, 0.0f, lev, y);
+                    }
+                    stg_nt(r, dst + j * 16);
+                }
+            };
+            if (fdiv) body(std::true_type{}); else body(std::false_type{});
+        } else {
+            bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
+        }
+    }
+}
+
+// no buckets: phases 1 and 2 do not depend on the level count (k_mg_minmax_opt, k_mg_fold); phase 3 with the tensor's own sm1
+template <int STOCH>
+__global__ __launch_bounds__(256) void k_mg_apply_lv(const QdTensorDesc* __restrict__ table, const int32_t* __restrict__ levels,
+                                                     int ntensors, int64_t total_tiles, const float* ab, float me, uint64_t seed,
+                                                     const uint64_t* __restrict__ seed_cell) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t seed0 = STOCH ? first_seed(seed, seed_cell) : 0;
+    Prep pp;
+    pp.mean = 0.0f;
+    pp.me = me;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdTensorDesc d = table[ti];
+        const float sm1 = (float)(levels[ti] - 1);
+        const uint64_t seed_t = seed0 + (uint64_t)ti;
+        const float a = ab[2 * ti], b = ab[2 * ti + 1];
+        const int64_t lo = (t - d.first_tile) * kTile;
+        const int64_t hi = lo + kTile < d.n ? lo + kTile : d.n;
+        float lev;
+        if (hi - lo == kTile && (((((uintptr_t)d.x) | ((uintptr_t)d.q)) & 15) == 0)) {
+            const f4* src = (const f4*)(d.x + lo) + lane;
+            f4* dst = (f4*)(d.q + lo) + lane;
+            const uint64_t blk0 = (uint64_t)(lo >> 2) + (uint64_t)lane;
+            f4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ldg_nt(src + j * 64);
+            __builtin_amdgcn_sched_barrier(0);          // all four loads in flight before the first use
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f4 c = prep4(v[j], pp);
+                f4 r;
+                if (STOCH) {
+                    float rnd[4];
+                    philox_uniform4(seed_t, blk0 + (uint64_t)(j * 64), rnd);
+                    r.x = qdq_stochastic(c.x, a, b, sm1, 0.0f, rnd[0], lev); r.y = qdq_stochastic(c.y, a, b, sm1, 0.0f, rnd[1], lev);
+                    r.z = qdq_stochastic(c.z, a, b, sm1, 0.0f, rnd[2], lev); r.w = qdq_stochastic(c.w, a, b, sm1, 0.0f, rnd[3], lev);
+                } else {
+                    r.x = qdq(c.x, a, b, sm1, 0.0f, lev); r.y = qdq(c.y, a, b, sm1, 0.0f, lev);
+                    r.z = qdq(c.z, a, b, sm1, 0.0f, lev); r.w = qdq(c.w, a, b, sm1, 0.0f, lev);
+                }
+                stg_nt(r, dst + j * 64);
+            }
+        } else {
+            for (int64_t i = lo + lane; i < hi; i += 64) {
+                const float c = prep(d.x[i], pp);
+                if (STOCH) {
+                    float r4[4];
+                    philox_uniform4(seed_t, (uint64_t)i >> 2, r4);
+                    d.q[i] = qdq_stochastic(c, a, b, sm1, 0.0f, r4[i & 3], lev);
+                } else {
+                    d.q[i] = qdq(c, a, b, sm1, 0.0f, lev);
+                }
+            }
+        }
+    }
+}
+
 // clamp != 0 needs a positive limit (not NaN); the limit the kernels see, +inf when the clamp is off
 inline bool clamp_limit(int clamp, float max_element, float& me) {
     me = clamp ? max_element : INFINITY;
@@ -473,6 +635,60 @@ int qd_multi_uniform_global_opt_f32(const QdTensorDesc* table, int ntensors, int
                            seed, seed_cell);
     else
         hipLaunchKernelGGL(k_mg_apply_opt<0>, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, alpha_beta, sm1, me,
+                           seed, seed_cell);
+    return (int)hipGetLastError();
+}
+
+int qd_multi_uniform_levels_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                int64_t bucket, int clamp, float max_element, int stochastic, uint64_t seed,
+                                const uint64_t* seed_cell, void* stream) {
+    float me;
+    if (!table || !levels || (((uintptr_t)levels) & 3) || ntensors <= 0 || total_tiles < 0 || bucket <= 0 ||
+        !clamp_limit(clamp, max_element, me))
+        return QD_ERR_INVALID_ARGUMENT;
+    if (seed_cell && (((uintptr_t)seed_cell) & 7)) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = blocks_for(total_tiles, 4);
+#define QD_MULTI_LV(ROW)                                                                                                 \
+    {                                                                                                                    \
+        if (stochastic)                                                                                                  \
+            hipLaunchKernelGGL((k_multi_uniform_lv<ROW, 1>), dim3(blocks), dim3(256), 0, st, table, levels, ntensors,    \
+                               total_tiles, bucket, me, seed, seed_cell);                                                \
+        else                                                                                                             \
+            hipLaunchKernelGGL((k_multi_uniform_lv<ROW, 0>), dim3(blocks), dim3(256), 0, st, table, levels, ntensors,    \
+                               total_tiles, bucket, me, seed, seed_cell);                                                \
+    }
+    if (bucket == 256) QD_MULTI_LV(256)
+    else if (bucket == 128) QD_MULTI_LV(128)
+    else if (bucket == 64) QD_MULTI_LV(64)
+    else QD_MULTI_LV(0)
+#undef QD_MULTI_LV
+    return check_launch();
+}
+
+int qd_multi_uniform_global_levels_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                       int clamp, float max_element, int stochastic, uint64_t seed, const uint64_t* seed_cell,
+                                       float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream) {
+    float me;
+    if (!table || !levels || (((uintptr_t)levels) & 3) || ntensors <= 0 || total_tiles < 0 || !alpha_beta ||
+        !clamp_limit(clamp, max_element, me))
+        return QD_ERR_INVALID_ARGUMENT;
+    if (seed_cell && (((uintptr_t)seed_cell) & 7)) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    if (!workspace || (((uintptr_t)workspace) & 15) || workspace_bytes < (size_t)total_tiles * 2 * sizeof(float))
+        return QD_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    int64_t b = (total_tiles + 3) / 4;
+    const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
+    hipLaunchKernelGGL(k_mg_minmax_opt, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, part, me);
+    hipLaunchKernelGGL(k_mg_fold, dim3(ntensors), dim3(256), 0, st, table, ntensors, total_tiles, part, alpha_beta);
+    if (stochastic)
+        hipLaunchKernelGGL(k_mg_apply_lv<1>, dim3(blocks), dim3(256), 0, st, table, levels, ntensors, total_tiles, alpha_beta, me,
+                           seed, seed_cell);
+    else
+        hipLaunchKernelGGL(k_mg_apply_lv<0>, dim3(blocks), dim3(256), 0, st, table, levels, ntensors, total_tiles, alpha_beta, me,
                            seed, seed_cell);
     return (int)hipGetLastError();
 }

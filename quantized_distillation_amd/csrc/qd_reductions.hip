@@ -6,6 +6,7 @@
 //   K7  qd_ste_bucket_backward_f32  uniformQuantization_variable.backward     :319-406
 //   K8  qd_clamp_f32, qd_truncated_ste_f32   the callers' 'truncated' STE     cnn_models/conv_forward_model.py:240-241,263-264
 //   K7m qd_multi_ste_plan, qd_multi_ste_backward_f32  K7 of every parameter in one launch   conv_forward_model.py:253-266
+//       qd_multi_ste_backward_levels_f32              the same with a level count per tensor (k_multi_ste_lv)
 // Its own translation unit so that hipcc builds it next to qd_kernels.hip / qd_nearest.hip / qd_scale.hip (parallel build).
 #include "qd_transform.h"      // shared helpers: workspace carving, launch geometry
 #include "qd_multi.h"          // owner_of, fill_prefix for K7m
@@ -979,6 +980,41 @@ __global__ __launch_bounds__(256) void k_multi_ste(const QdSteDesc* __restrict__
     }
 }
 
+// k_multi_ste with a level count per tensor: levels[ti] is read with the descriptor (wave-uniform, a scalar load), and sm1,
+// use_tab and tab -- the same correctly rounded division -- are derived whenever the wave moves on to another tensor.  The
+// tile -> bucket map and both bodies are those of k_multi_ste, so every bucket is summed in the per-tensor call's order.
+template <int LPB, int V>
+__global__ __launch_bounds__(256) void k_multi_ste_lv(const QdSteDesc* __restrict__ table, const int32_t* __restrict__ levels,
+                                                      int ntensors, int64_t total_tiles, int64_t bucket, int tie_mode) {
+    constexpr int ROW = LPB * V * 4;                  // 0: no register path at this bucket size
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    int cur = -1;                                   // the tensor sm1 / use_tab / tab below belong to
+    float sm1 = 1.0f, tab = 0.0f;
+    bool use_tab = false;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdSteDesc d = table[ti];                                  // (an empty tensor owns no tile)
+        if (d.n <= 0) continue;
+        if (ti != cur) {
+            cur = ti;
+            sm1 = (float)(levels[ti] - 1);
+            use_tab = sm1 <= 15.0f;
+            tab = (float)(lane & 15) / sm1;
+        }
+        const int64_t local = t - d.first_tile;
+        const SteCut c = ste_cut<ROW>(d.x, d.g, d.out, d.n, bucket);
+        if (local < c.vtiles) {
+            if constexpr (LPB > 0) ste_vec_tile<LPB, V>(d.x, d.g, d.out, c.nfull, local, lane / LPB, lane % LPB, sm1, tie_mode,
+                                                         use_tab, tab);
+        } else {
+            const int64_t bkt = c.nfull + (local - c.vtiles);   // (a tile count that does not belong to this table reaches no bucket)
+            if (local >= 0 && bkt * c.row < d.n) ste_wave_bucket(d.x, d.g, d.out, d.n, c.row, bkt, lane, sm1, tie_mode);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1205,6 +1241,26 @@ int qd_multi_ste_backward_f32(const QdSteDesc* table, int ntensors, int64_t tota
 #undef QD_MULTI_STE
     if (!ste_lanes_per_bucket(bucket))
         hipLaunchKernelGGL((k_multi_ste<0, 0>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, sm1, tie_mode);
+    return check_launch();
+}
+
+int qd_multi_ste_backward_levels_f32(const QdSteDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                     int64_t bucket, int tie_mode, void* stream) {
+    if (!table || !levels || (((uintptr_t)levels) & 3) || ntensors <= 0 || total_tiles < 0 || bucket <= 0)
+        return QD_ERR_INVALID_ARGUMENT;
+    if (tie_mode != QD_STE_TIE_REFERENCE && tie_mode != QD_STE_TIE_TRUE_ARG) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = blocks_for(total_tiles, 4);
+#define QD_MULTI_STE_LV(ROW, LPB, V)                                                                                     \
+    if (bucket == ROW)                                                                                                   \
+        hipLaunchKernelGGL((k_multi_ste_lv<LPB, V>), dim3(blocks), dim3(256), 0, st, table, levels, ntensors, total_tiles, \
+                           bucket, tie_mode);
+    QD_STE_SHAPES(QD_MULTI_STE_LV)
+#undef QD_MULTI_STE_LV
+    if (!ste_lanes_per_bucket(bucket))
+        hipLaunchKernelGGL((k_multi_ste_lv<0, 0>), dim3(blocks), dim3(256), 0, st, table, levels, ntensors, total_tiles, bucket,
+                           tie_mode);
     return check_launch();
 }
 

@@ -20,11 +20,30 @@ import torch
 from . import _lib
 
 
+def _level_counts(s, tensors):
+    """s of the uniform one-launch classes: an integer >= 2 for every tensor, or a sequence of them, one per tensor.  Returns
+    (what `self.s` keeps: the int or a tuple, the list of tensors); only the list's length is looked at, no tensor is."""
+    def one(v):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or int(v) != v or v < 2:
+            raise ValueError('s must be an integer >= 2, or a sequence of them with one entry per tensor')
+        return int(v)
+    if isinstance(s, numbers.Real) and not isinstance(s, bool):
+        return one(s), tensors
+    if isinstance(s, (str, bytes)) or not hasattr(s, '__iter__'):
+        raise ValueError('s must be an integer >= 2, or a sequence of them with one entry per tensor')
+    counts = tuple(one(v) for v in s)
+    tensors = list(tensors)
+    if len(counts) != len(tensors):
+        raise ValueError('s has %d entries for %d tensors: need one per tensor' % (len(counts), len(tensors)))
+    return counts, tensors
+
+
 class _DeviceTable(object):
     """What the one-launch classes share: the argument check, the descriptor table on the device, and the launch on a table
     that is current.  A subclass names its descriptor type, says which tensors go into which field (_columns), calls the
     library's plan (_plan_table) and makes the launch calls."""
     _DESC = None           # the ctypes descriptor type (_lib.Qd*Desc)
+    entry_point = None     # name of the C entry point the last launch went through (_entry)
     _WATCH = ()            # attributes holding the tensors a caller may rebind: the table is rebuilt when one of them moved
 
     def _adopt(self, first_contiguous=True, **named):
@@ -86,6 +105,21 @@ class _DeviceTable(object):
             _lib.mark_written(written)     # one native call bumps their version counters
         return written
 
+    def _entry(self, name):
+        """The C entry point a launch goes through; `entry_point` keeps the name of the last one taken."""
+        self.entry_point = name
+        return getattr(_lib.load(), name)
+
+    def _bind_levels(self, s):
+        """s as _level_counts returned it, once self.device is known.  Sets self.s, self._s (the one level count of the
+        existing entry points: a scalar s, or a sequence whose entries are all equal -- such an object launches exactly what
+        it always launched) and self._levels: None, or for a mixed sequence one int32 device array, entry i for tensor i.
+        The array is the object's own and outlives every re-plan of the table (the entries go by position, not by pointer)."""
+        self.s = s
+        mixed = isinstance(s, tuple) and len(set(s)) > 1
+        self._s = None if mixed else (s[0] if isinstance(s, tuple) else s)
+        self._levels = torch.tensor(s, dtype=torch.int32, device=self.device) if mixed else None
+
 
 class MultiTensorQuantizer(_DeviceTable):
     """uniformQuantization(t, s, bucket_size=bucket_size, stochastic_rounding=..., max_element=...)[0] of every tensor, written
@@ -99,7 +133,13 @@ class MultiTensorQuantizer(_DeviceTable):
     seed_on_device=True keeps seed0 in `seed_cell`, one int64 device word that reseed() writes and every quantize() advances
     by n_tensors on the launch's stream: nothing on the host is consulted, so the call can be captured and each replay
     draws anew -- launch r after a reseed uses seed0 + r * n_tensors + i (int64 wrap-around gives the bits of uint64).
-    subtract_mean is not offered: call uniformQuantization per tensor for it."""
+    subtract_mean is not offered: call uniformQuantization per tensor for it.
+
+    s: one level count for every tensor, or a sequence with one entry per tensor (per-layer bit widths: tensor i equals
+    uniformQuantization(t_i, s[i], ...)); `self.s` keeps the int or a tuple.  A sequence of unequal entries is uploaded once
+    as an int32 device array and every option combination launches qd_multi_uniform_levels_f32 /
+    qd_multi_uniform_global_levels_f32; a scalar, or a sequence whose entries are all equal, launches what it always
+    launched.  `entry_point` names the C entry point the last quantize() went through."""
     _DESC = _lib.QdTensorDesc
     _WATCH = ('inputs', 'outputs')
 
@@ -107,8 +147,7 @@ class MultiTensorQuantizer(_DeviceTable):
                  subtract_mean=False, seed_on_device=False):
         if bucket_size is not None and (not isinstance(bucket_size, int) or bucket_size <= 0):
             raise ValueError('bucket_size must be a positive integer or None')
-        if int(s) != s or s < 2:
-            raise ValueError('s must be an integer >= 2')
+        s, tensors = _level_counts(s, tensors)
         if max_element is not False and (max_element is True or not isinstance(max_element, numbers.Number)):
             raise ValueError('maxElementAllowed must be a number')                  # as ScalingFunction, ref: :31-33
         if subtract_mean:
@@ -116,7 +155,6 @@ class MultiTensorQuantizer(_DeviceTable):
                                       'call quantization.uniformQuantization(t, s, subtract_mean=True, ...) per tensor')
         if seed_on_device and not stochastic_rounding:
             raise ValueError('seed_on_device=True needs stochastic_rounding=True')
-        self.s = int(s)
         self.bucket_size = bucket_size
         self.stochastic_rounding = bool(stochastic_rounding)
         self.max_element = max_element
@@ -128,6 +166,7 @@ class MultiTensorQuantizer(_DeviceTable):
             self.outputs = [torch.empty_like(t) for t in self.inputs]
         else:
             self.inputs, self.outputs = self._adopt(tensors=tensors, outputs=outputs)
+        self._bind_levels(s)
         self._plan()
         if self.seed_on_device:
             self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -149,22 +188,31 @@ class MultiTensorQuantizer(_DeviceTable):
 
     def _call(self):
         if self.bucket_size is None:
-            return _lib.load().qd_multi_uniform_global_f32(
-                self._table.data_ptr(), self.n_tensors, self._tiles, self.s, self.alpha_beta.data_ptr(),
+            return self._entry('qd_multi_uniform_global_f32')(
+                self._table.data_ptr(), self.n_tensors, self._tiles, self._s, self.alpha_beta.data_ptr(),
                 self._scratch.data_ptr(), self._scratch.numel() * 4, _lib.stream_ptr(self.device))
-        return _lib.load().qd_multi_uniform_f32(self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s,
+        return self._entry('qd_multi_uniform_f32')(self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self._s,
                                                 _lib.stream_ptr(self.device))
 
     def _call_opt(self, seed):
         clamp, me = (0, 0.0) if self.max_element is False else (1, float(self.max_element))
         cell = self.seed_cell.data_ptr() if self.seed_on_device else None
+        if self._levels is not None:               # a level count per tensor: the one pair of entry points for every option
+            if self.bucket_size is None:
+                return self._entry('qd_multi_uniform_global_levels_f32')(
+                    self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, clamp, me,
+                    int(self.stochastic_rounding), seed, cell, self.alpha_beta.data_ptr(), self._scratch.data_ptr(),
+                    self._scratch.numel() * 4, _lib.stream_ptr(self.device))
+            return self._entry('qd_multi_uniform_levels_f32')(
+                self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, clamp, me,
+                int(self.stochastic_rounding), seed, cell, _lib.stream_ptr(self.device))
         if self.bucket_size is None:
-            return _lib.load().qd_multi_uniform_global_opt_f32(
-                self._table.data_ptr(), self.n_tensors, self._tiles, self.s, clamp, me, int(self.stochastic_rounding), seed,
+            return self._entry('qd_multi_uniform_global_opt_f32')(
+                self._table.data_ptr(), self.n_tensors, self._tiles, self._s, clamp, me, int(self.stochastic_rounding), seed,
                 cell, self.alpha_beta.data_ptr(), self._scratch.data_ptr(), self._scratch.numel() * 4,
                 _lib.stream_ptr(self.device))
-        return _lib.load().qd_multi_uniform_opt_f32(
-            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s, clamp, me,
+        return self._entry('qd_multi_uniform_opt_f32')(
+            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self._s, clamp, me,
             int(self.stochastic_rounding), seed, cell, _lib.stream_ptr(self.device))
 
     def reseed(self, seed0=None):
@@ -184,7 +232,7 @@ class MultiTensorQuantizer(_DeviceTable):
         launch (default: the next n_tensors seeds of the process counter); kept as `last_seed`."""
         if seed is not None and (not self.stochastic_rounding or self.seed_on_device):
             raise ValueError('seed= is for stochastic_rounding=True with the seed passed by value (seed_on_device=False)')
-        if not self.stochastic_rounding and self.max_element is False:
+        if not self.stochastic_rounding and self.max_element is False and self._levels is None:
             return self._launch(self._call, self.outputs, check_pointers)
         seed0 = 0
         if self.stochastic_rounding and not self.seed_on_device:
@@ -287,6 +335,9 @@ class MultiTensorSTE(_DeviceTable):
         backward(): grads[i] -> outs[i] for every i (in place by default: outs = grads)
     `weights[i]` are the full-precision values the forward quantized.  Each result is bit-identical to
     ste.ste_bucket_backward(weights[i], grads[i], bucket_size, s, out=outs[i], tie_mode=tie_mode).
+    s: one level count, or a sequence with one entry per tensor (s[i] in the call above), as MultiTensorQuantizer takes it:
+    unequal entries launch qd_multi_ste_backward_levels_f32, anything else the entry point above (`entry_point` names the one
+    the last backward() took).
     """
     _DESC = _lib.QdSteDesc
     _WATCH = ('weights', 'grads', 'outs')
@@ -297,11 +348,10 @@ class MultiTensorSTE(_DeviceTable):
                                       ' Not hard to modify though')
         if isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0:
             raise ValueError('bucket_size must be a positive integer')
-        if int(s) != s or s < 2:
-            raise ValueError('s must be an integer >= 2')
+        s, weights = _level_counts(s, weights)
         if tie_mode not in ('reference', 'true_arg'):
             raise ValueError("tie_mode must be 'reference' or 'true_arg'")
-        self.s, self.bucket_size = int(s), bucket_size
+        self.bucket_size = bucket_size
         self.tie_mode = 0 if tie_mode == 'reference' else 1
         # OWNING references: the device table holds raw pointers into these tensors
         if outs is None:
@@ -309,6 +359,7 @@ class MultiTensorSTE(_DeviceTable):
             self.outs = self.grads
         else:
             self.weights, self.grads, self.outs = self._adopt(weights=weights, grad=grads, out=outs)
+        self._bind_levels(s)
         self._plan()
 
     def _columns(self):
@@ -321,6 +372,10 @@ class MultiTensorSTE(_DeviceTable):
 
     def backward(self, check_pointers=True):
         """out = the bucket-aware STE gradient for every tensor (one launch).  Returns the list of outs."""
-        return self._launch(lambda: _lib.load().qd_multi_ste_backward_f32(
-            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.s, self.tie_mode,
+        if self._levels is not None:
+            return self._launch(lambda: self._entry('qd_multi_ste_backward_levels_f32')(
+                self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.tie_mode,
+                _lib.stream_ptr(self.device)), self.outs, check_pointers)
+        return self._launch(lambda: self._entry('qd_multi_ste_backward_f32')(
+            self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self._s, self.tie_mode,
             _lib.stream_ptr(self.device)), self.outs, check_pointers)
