@@ -189,6 +189,15 @@ PyObject* glue_uniform(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
 // are made when sf.alpha / sf.beta are read), launch qd_uniform_f32, and build the ScalingFunction instance directly
 // (its class-level defaults cover every field the call does not set).  Anything else returns None and the caller takes
 // the general path, which also raises the reference's exceptions for bad arguments.
+//
+// Under stream capture (torch.cuda.graph) the slab is not touched: a captured launch writes only memory that the graph's
+// pool or a live Python object owns.  A slab is owned by g_slabs and by the objects carved from it and nothing ties its
+// life to a graph's: the loops drop the ScalingFunction, the next roll-over returns the slab to the caching allocator,
+// and every replay would write alpha / beta over whoever was handed the block next.  While the stream is capturing the
+// pair therefore comes from a tensor of the call's own (the [2, nb, 1] / [2, 1] branch of requests above a quarter
+// slab): allocated from the graph's private pool, read through _ab -- no copy on first read, so a kept ScalingFunction
+// shows the pair of the latest replay, as one from the general path does -- and g_slabs is left as the eager calls left
+// it.  The query is one hipStreamIsCapturing per call, the form launch_single (qd_transform.h) already uses.
 PyTypeObject* g_sf_type = nullptr;
 PyObject *s_bucket_size, *s_n, *s_ab, *s_ab_slab, *s_ab_off, *s_arg_source, *s_arg_version, *s_mean_tensor, *s_zero;
 
@@ -201,6 +210,12 @@ struct Slab {
 };
 std::vector<Slab> g_slabs;
 constexpr int64_t kSlabFloats = 1 << 18;          // 1 MiB; requests above a quarter of it get their own allocation
+
+// A status that cannot be read counts as capturing: a tensor of the call's own is right in either case.
+inline bool is_capturing(void* stream) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(static_cast<hipStream_t>(stream), &status) != hipSuccess || status != hipStreamCaptureStatusNone;
+}
 
 PyObject* glue_register(PyObject*, PyObject* type) {
     if (!PyType_Check(type)) {
@@ -255,7 +270,7 @@ PyObject* glue_uniform_common(PyObject*, PyObject* const* args, Py_ssize_t nargs
     float* abp = nullptr;
     PyObject* ab_owner = nullptr;                          // new reference: the slab's wrapper or a dedicated [2, nb, 1] tensor
     int64_t ab_off = -1;
-    if (need <= kSlabFloats / 4) {
+    if (need <= kSlabFloats / 4 && !is_capturing(stream)) {
         Slab* sl = nullptr;
         for (auto& c : g_slabs)
             if (c.device == dev.index() && c.stream == stream) { sl = &c; break; }
@@ -483,6 +498,21 @@ PyObject* glue_host_cost_probe(PyObject*, PyObject* const* args, Py_ssize_t narg
     END_HANDLE_TH_ERRORS
 }
 
+// capture_query_probe(iters) -> us per capture-status query on torch's current stream of the current device: what every
+// call of uniform_common pays to keep captured launches off the slab.  Measurement aid, as host_cost_probe.
+PyObject* glue_capture_query_probe(PyObject*, PyObject* arg) {
+    HANDLE_TH_ERRORS
+    const long iters = PyLong_AsLong(arg);
+    if (PyErr_Occurred()) return nullptr;
+    void* stream = c10::hip::getCurrentHIPStream(c10::hip::current_device()).stream();
+    long capturing = 0;
+    const auto a = std::chrono::steady_clock::now();
+    for (long i = 0; i < iters; ++i) capturing += is_capturing(stream);
+    const auto b = std::chrono::steady_clock::now();
+    return Py_BuildValue("(dl)", std::chrono::duration<double, std::micro>(b - a).count() / (iters > 0 ? iters : 1), capturing);
+    END_HANDLE_TH_ERRORS
+}
+
 // mark_written(t | sequence of tensors): for the entry points bound with ctypes (in-place scale_down / inv_scale_down, the
 // STE kernels, the multi-tensor launches), whose outputs torch has not seen being written.
 PyObject* glue_mark_written(PyObject*, PyObject* arg) {
@@ -521,6 +551,8 @@ PyMethodDef methods[] = {
      "point_grad(g, idx, alpha, bucket, k) -> grad_points"},
     {"host_cost_probe", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(glue_host_cost_probe)), METH_FASTCALL,
      "host_cost_probe(x, levels, bucket, iters) -> (launch us, allocation us, both us): host time per call"},
+    {"capture_query_probe", glue_capture_query_probe, METH_O,
+     "capture_query_probe(iters) -> (us per capture-status query on the current stream, how many said 'capturing')"},
     {"abi_version", glue_abi_version, METH_NOARGS, "QD_ABI_VERSION of the include/qd_hip.h this module was compiled against"},
     {nullptr, nullptr, 0, nullptr}};
 

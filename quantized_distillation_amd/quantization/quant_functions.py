@@ -107,7 +107,7 @@ class ScalingFunction(object):
     _n = None
     _ab = None                     # [2, nb, 1] / [2, 1]: alpha and beta in one allocation, split on first access
     _ab_slab = None                # ... or 2 * nb floats at offset _ab_off of a slab shared by many calls (glue.uniform_common)
-    _ab_off = None
+    _ab_off = None                 # (eager calls only: under stream capture that entry point sets _ab, a tensor the graph's pool owns)
     _alpha = None
     _beta = None
     _idx_min_rows = None
