@@ -190,7 +190,9 @@ int qd_point_grad_f32(const float* g, const void* idx, int idx_bytes, const floa
 /* K7: 'complicated' straight-through backward of uniformQuantization_variable
  * (quant_functions.py:319-406, intended math): per bucket
  *     S_b = sum_i g_i*(qs_i - u_i);  out = g;  out[jmax_b] += S_b;  out[jmin_b] -= S_b.
- * Requires bucket > 0 (as the reference does, :332-334).  out may alias g. */
+ * Every term is the reference's own sequence of fp32 operations with IEEE quotients (the bucket-invariant division only in
+ * buckets where it equals them: alpha_q in [2^-60, 2^100], every non-zero x - beta_q >= max(2^-100, alpha_q 2^-120)); only
+ * the order of the fp32 sum differs.  Requires bucket > 0 (as the reference does, :332-334).  out may alias g. */
 int qd_ste_bucket_backward_f32(const float* x, const float* g, float* out, int64_t n, int64_t bucket, int levels,
                                int tie_mode, void* stream);
 
@@ -470,7 +472,8 @@ int qd_order_stats_f32(const float* x, int64_t n, const int64_t* ranks, int m, f
 /* ---- self test of the bucket-invariant division (csrc/qd_selftest.hip).  The quantize kernels replace the IEEE division
  * u = (x - beta) / alpha of quantization/quant_functions.py:106-107 by y = RN(1/alpha) once per bucket and two FMAs per
  * element (qd_common.h: div_alpha<true>), which must give the correctly rounded quotient bit for bit wherever it is used:
- * alpha in [2^-60, 2^100], n = 0 or n >= 2^-100 -- and, where the quotient itself is returned (qd_scale_down_f32), n >=
+ * alpha in [2^-60, 2^100], n = 0 or n >= 2^-100 -- and, where the quotient itself is consumed (qd_scale_down_f32,
+ * qd_scale_digitize_histogram_f32, the terms of qd_ste_bucket_backward_f32 / qd_multi_ste_backward_f32), n >=
  * alpha 2^-120 as well (a normal quotient).  This entry point generates `npairs` adversarial (n, alpha) pairs of
  * `family` 0 .. 5 on the device (0: the quantizer's own domain, 1: wide exponents, 2: all-ones / near-power-of-two
  * significands, 3: near-exact quotients around level and half-level values, 4: the edges of the stated ranges, 5: small

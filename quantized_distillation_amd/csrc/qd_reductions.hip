@@ -652,9 +652,14 @@ __global__ __launch_bounds__(256) void k_point_grad_final(const float* part, int
 // reference, but 3e-7 / 6e-6 of sum|t| away from THE REFERENCE at 16 / 256 levels, because the reference's two quotients
 // are rounded before they are subtracted.)  The two quotients per element use the bucket-invariant division (three VALU
 // operations each, qd_common.h); here the quotient itself is consumed, so the form is only taken when it is exact for
-// every numerator of the bucket: alpha_q in [2^-60, 2^100] and no numerator in (0, 2^-100) -- a wave-uniform choice,
-// otherwise the IEEE division.  The level of each element (the only thing q depends on) comes from the same shortcuts as
-// K1: bucket-invariant division of (x - beta) / alpha, and level / (s-1) from the per-row table for <= 16 levels.
+// every numerator of the bucket: alpha_q in [2^-60, 2^100] and no numerator x - beta_q in (0, max(2^-100, alpha_q 2^-120))
+// -- scale_down's own condition (scale_fast_ok, qd_common.h): below 2^-100 the remainder underflows, and below
+// alpha_q 2^-120 the quotient is DENORMAL and can differ from the IEEE one in its last bit, which an incoming gradient of
+// 2^100 turns into half of the bucket sum -- a wave-uniform choice, otherwise the IEEE division.  Only the numerators
+// x - beta_q are looked at: the others, q - beta_q, are 0 or at least one level step, about alpha_q / (s - 1), whose quotient
+// is normal and which is far above 2^-100 for alpha_q >= 2^-60.  The level of each element (the only thing q depends on)
+// comes from the same shortcuts as K1: bucket-invariant division of (x - beta) / alpha, and level / (s-1) from the per-row
+// table for <= 16 levels.
 template <bool FAST>
 __device__ __forceinline__ float ste_term(float g, float q, float x, float aq, float bq, float yq) {
     float qs = q - bq;  qs = div_alpha<FAST>(qs, aq, yq);
@@ -662,10 +667,10 @@ __device__ __forceinline__ float ste_term(float g, float q, float x, float aq, f
     const float d = qs - u;
     return g * d;
 }
-__device__ __forceinline__ bool ste_tiny_numerator(float x, float bq) {     // 0 < |x - beta_q| < 2^-100: outside the proven range
-    const float n = fabsf(x - bq);
-    return n < 0x1p-100f && n != 0.0f;
-}
+// The key of scale_numerator_key (qd_common.h) for the numerator x - beta_q; a lane keeps the unsigned minimum over its
+// elements and scale_fast_ok(alpha_q, min) decides.  beta_q is the bucket's minimum (level 0 dequantizes to beta exactly), so
+// the numerator is >= 0; fabsf keeps the key meaningful should that ever change.
+__device__ __forceinline__ unsigned ste_numerator_key(float x, float bq) { return __float_as_uint(fabsf(x - bq)) - 1u; }
 
 // vector path: LPB lanes per bucket, V float4 per lane, the whole bucket (x, g, q) in registers, one pass.  Index ties:
 // the FIRST element (in memory order) at the top / bottom level of the quantized bucket (or the true arg of x).
@@ -723,13 +728,13 @@ __device__ __forceinline__ void ste_vec_tile(const float* x, const float* g, flo
         int jmax = 0x7fffffff, jmin = 0x7fffffff;           // index inside the bucket
         const bool ref_tie = tie_mode == QD_STE_TIE_REFERENCE;
         const bool bad = ref_tie ? (qmn != qmn) : (mn != mn);   // the searched tensor's min / max are NaN: both sit at its first NaN
-        bool tiny = false;
+        unsigned nkey = 0xFFFFFFFFu;                        // min over the lane's numerators x - beta_q
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             const int base = (j * LPB + l) * 4;
 #define QD_STE_ELEM(c, off)                                                          \
             {                                                                        \
-                tiny |= ste_tiny_numerator(xv[j].c, bq);                             \
+                nkey = min(nkey, ste_numerator_key(xv[j].c, bq));                    \
                 const float sv = ref_tie ? qv[j].c : xv[j].c;                        \
                 const bool top = bad ? (sv != sv) : (sv == (ref_tie ? qmx : mx));    \
                 const bool bot = bad ? (sv != sv) : (sv == (ref_tie ? qmn : mn));    \
@@ -751,7 +756,7 @@ __device__ __forceinline__ void ste_vec_tile(const float* x, const float* g, flo
                 sum += ste_term<FAST>(gv[j].w, qv[j].w, xv[j].w, aq, bq, yq);
             }
         };
-        if (!__any(!fastdiv_ok(aq) || tiny)) bucket_sum(std::true_type{}); else bucket_sum(std::false_type{});
+        if (!__any(!scale_fast_ok(aq, nkey))) bucket_sum(std::true_type{}); else bucket_sum(std::false_type{});
         sum = group_sum<LPB>(sum); jmax = group_imin<LPB>(jmax); jmin = group_imin<LPB>(jmin);
         const bool touch = jmax != jmin || bad;             // constant bucket: +S and -S cancel; a NaN bucket: (g + S) - S = NaN there
 #pragma unroll
@@ -801,7 +806,8 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, 
         alpha_beta(mn, mx, a, b);
         // pass 2: min/max of the QUANTIZED bucket (the reference re-runs scale_down on q, :350)
         float qmn = INFINITY, qmx = -INFINITY;
-        bool tiny = false, qnan = false;
+        bool qnan = false;
+        unsigned nkey = 0xFFFFFFFFu;
         for (int64_t i = lo + lane; i < hi; i += 64) {
             float lev;
             const float q = qdq(x[i], a, b, sm1, 0.0f, lev);
@@ -812,7 +818,7 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, 
         float aq, bq;
         alpha_beta(qmn, qmx, aq, bq);
         const bool bad = tie_mode == QD_STE_TIE_REFERENCE ? (qmn != qmn) : (mn != mn);   // min / max of the searched tensor are NaN: both at its first NaN
-        for (int64_t i = lo + lane; i < hi; i += 64) tiny |= ste_tiny_numerator(x[i], bq);
+        for (int64_t i = lo + lane; i < hi; i += 64) nkey = min(nkey, ste_numerator_key(x[i], bq));
         // pass 3: S_b (the reference's own per-element operations, :400) and the first index at the top / bottom level
         // (or the true arg of x)
         float s = 0.0f;
@@ -832,7 +838,7 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, 
                 if (bot && (long long)i < jmin) jmin = i;
             }
         };
-        if (!__any(!fastdiv_ok(aq) || tiny)) pass3(std::true_type{}); else pass3(std::false_type{});
+        if (!__any(!scale_fast_ok(aq, nkey))) pass3(std::true_type{}); else pass3(std::false_type{});
         s = wave_sum(s);
         jmax = wave_min_ll(jmax);
         jmin = wave_min_ll(jmin);

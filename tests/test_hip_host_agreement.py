@@ -64,6 +64,23 @@ def test_device_and_host_library_agree(n, bucket):
     assert not torch.equal(qh, quantization.uniformQuantization(x, 16, bucket_size=bucket)[0])      # (and it IS the stochastic branch)
 
 
+@pytest.mark.parametrize('bucket', [64, 256, 1024, 33, 100, 1000])
+def test_ste_backward_agrees_on_denormal_quotients(bucket):
+    """The STE leg on the pair buckets of tests/extreme_scale_cases.py (a denormal quotient n / alpha_q on which the
+    bucket-invariant division differs from the IEEE one), one term per bucket sum so that no order is involved: the device
+    library and the host library -- which divides by IEEE -- give the same bits, both tie modes."""
+    import extreme_scale_cases as C
+    for with_beta in (False, True):
+        x = torch.from_numpy(C.pair_tensor(bucket, with_beta))
+        gr = torch.from_numpy(C.pair_gradient(bucket, x.numel(), dense=False))
+        for s in (4, 16, 256):
+            for tie_mode in ('reference', 'true_arg'):
+                oh = ste.ste_bucket_backward(x, gr, bucket, s, tie_mode=tie_mode)
+                od = ste.ste_bucket_backward(x.to(DEV), gr.to(DEV), bucket, s, tie_mode=tie_mode)
+                assert torch.equal(od.cpu(), oh), (bucket, with_beta, s, tie_mode, int((od.cpu() != oh).sum()))
+                assert int((oh != gr).sum()) == 2 * (-(-x.numel() // bucket))      # +S and -S in every bucket: S != 0
+
+
 @pytest.mark.parametrize('bucket', [256, 100, None, 33])
 def test_device_and_host_library_agree_on_nonfinite_inputs(bucket):
     """test_device_and_host_library_agree on the non-finite inputs of tests/golden/nonfinite_paths.npz (3000 elements): the

@@ -216,6 +216,48 @@ def test_bucket_invariant_division_in_exact_arithmetic():
     assert st['denormal'][0] > 500
 
 
+def test_committed_denormal_quotient_pairs_are_what_they_claim():
+    """tests/golden/div_denormal_pairs.json (the inputs of tests/test_hip_extreme_scales.py) re-derived in exact rational
+    arithmetic: every pair has alpha in [2^-60, 2^100], n >= 2^-100, a denormal IEEE quotient, and the shortcut's result
+    differs from it -- with the recorded values; at least 48 pairs over quotient exponents down to -148 and up to -128, the
+    four of the issue that introduced them included.  And the buckets tests/extreme_scale_cases.py builds around them give
+    numpy's IEEE division exactly that numerator and that divisor."""
+    import json
+    import os
+    import sys
+    from fractions import Fraction
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.join(os.path.dirname(here), 'tools'))
+    import div_invariant_check as dic
+    import extreme_scale_cases as C
+    from oracle import oracle_np as onp
+    with open(C.PAIRS_JSON) as f:
+        pairs = json.load(f)['pairs']
+    assert len(pairs) >= 48 and len({(p['n_bits'], p['alpha_bits']) for p in pairs}) == len(pairs)
+    exps = set()
+    for p in pairs:
+        n, a = dic.f32_fraction(int(p['n_bits'], 16)), dic.f32_fraction(int(p['alpha_bits'], 16))
+        assert Fraction(2) ** -60 <= a <= Fraction(2) ** 100 and n >= Fraction(2) ** -100, p
+        u, want = dic.div_invariant_exact(n, a)
+        assert u != want and 0 < want < Fraction(2) ** -126, p
+        assert float(u) == p['shortcut'] and float(want) == p['ieee'], p
+        assert Fraction(2) ** p['quotient_exponent'] <= want < Fraction(2) ** (p['quotient_exponent'] + 1), p
+        exps.add(p['quotient_exponent'])
+    assert exps >= set(range(-148, -127)), sorted(exps)
+    have = {(int(p['n_bits'], 16), int(p['alpha_bits'], 16)) for p in pairs}
+    assert {(0x25ffffff, 0x702aaaaa), (0x2d800001, 0x6dc00000), (0x1380fde1, 0x53c00000), (0x18aa2ae5, 0x58c00000)} <= have
+    ieee = np.array([p['ieee'] for p in pairs], dtype=np.float32)
+    for bucket in (33, 256):
+        for with_beta in (False, True):
+            x = C.pair_tensor(bucket, with_beta)
+            sd = onp.scale_down(x, bucket)
+            pn, _, _ = C.pair_positions(bucket, x.size)
+            assert np.array_equal(sd['u'].reshape(-1)[pn[:-1]], ieee), (bucket, with_beta)
+            assert np.array_equal(sd['alpha'].reshape(-1)[:-1], np.array([a for _, a in C.pairs()], np.float32))
+            sq = onp.scale_down(onp.uniform_quantize(x, 16, bucket)['q'], bucket)          # K7 re-scales the QUANTIZED tensor
+            assert np.array_equal(sq['alpha'], sd['alpha']) and np.array_equal(sq['beta'], sd['beta']), (bucket, with_beta)
+
+
 def test_committed_bench_lines_keep_the_contract_and_are_self_consistent():
     """The bench.py runs committed under profiles/ (round 6: the stdout line as the driver sees it + the full record that went
     to bench_detail.json): the line is one JSON object of at most 4096 bytes that parses from the last 6000 bytes of stdout,

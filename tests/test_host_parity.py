@@ -16,6 +16,7 @@ import torch
 
 import quantization
 import quantization.help_functions as qhf
+import test_hip_extreme_scales as E
 import test_hip_parity as P
 from oracle import oracle_c as oc
 from oracle import ref_stage
@@ -29,6 +30,10 @@ CPU_TESTS = [
     P.test_nonfinite_inputs_golden, P.test_nonuniform_options_golden, P.test_lazy_arg_indices_raise_after_the_source_was_modified,
     P.test_nonuniform_single_bucket_of_exactly_bucket_size, P.test_quantize_bit_exact_at_extreme_scales,
     P.test_scale_down_bit_exact_at_extreme_scales, P.test_stochastic_rounding_statistics,
+    # tests/test_hip_extreme_scales.py: denormal quotients and alpha on the boundaries of the bucket-invariant division
+    E.test_ste_backward_one_term_per_bucket_is_bit_exact_on_denormal_quotients,
+    E.test_ste_backward_dense_gradient_within_the_bucket_sum_tolerance, E.test_scale_down_bit_exact_on_denormal_quotients,
+    E.test_quantize_on_the_alpha_boundaries, E.test_quantize_without_buckets_on_the_alpha_boundaries,
 ]
 
 
