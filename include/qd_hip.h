@@ -86,7 +86,7 @@ extern "C" {
  * changed meaning).  qd_multi_dq_plan / qd_multi_nearest_f32 / qd_multi_point_grad_f32 take bucket == 0, buckets that are
  * no power of two and k up to 256, also without a bump: arguments that were rejected are now accepted; nothing existing
  * changed meaning.  qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 / qd_multi_ste_backward_levels_f32 (a level
- * count per tensor) are new symbols, likewise without a bump.
+ * count per tensor) are new symbols, likewise without a bump; so is qd_transform_plan (host only).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -111,6 +111,41 @@ int qd_set_single_fused_mode(int mode);
 /* Number of buckets / padded length of the bucket view (help_functions.py:67-94). Host only. */
 int64_t qd_num_buckets(int64_t n, int64_t bucket);
 int64_t qd_padded_length(int64_t n, int64_t bucket);
+
+/* Which kernel(s) a call of qd_uniform_f32 / qd_scale_down_f32 / qd_nearest_point_f32 reaches, and with what launch geometry.
+ * Host only, no device and no runtime call: the launcher of those three entry points runs the same function
+ * (csrc/qd_plan.h: plan_transform) on the same numbers and launches what it returns, so the answer is the launch -- checked for
+ * every bucket size on a machine without a GPU (tests/test_transform_plan.py), and against a trace on one
+ * (profiles/dispatch_map.txt).  Pointers enter as alignment facts, the device as its compute-unit count, so the result does not
+ * depend on the machine.  A new symbol (no ABI bump).
+ * qd_transform_plan(queries, count, plans) fills plans[i] for queries[i]; returns 0, or QD_ERR_INVALID_ARGUMENT (nothing
+ * written) for a null table, a mode outside 0 .. 2, n < 1, bucket < 0 or cus < 1 in any query. */
+typedef struct QdTransformQuery {
+    int32_t mode;            /* 0 qd_uniform_f32, 1 qd_scale_down_f32, 2 qd_nearest_point_f32                               */
+    int32_t data_misalign;   /* (address of x | address of q / u) & 15; the data pointers need 4-byte alignment              */
+    int32_t side_bytes;      /* level_idx asked for: 1; idx asked for: idx_bytes (1 or 8); 0: neither                        */
+    int32_t side_misalign;   /* its address & 15 (level_idx needs 4-byte alignment, an int64 idx 16)                         */
+    int32_t k, assign_mode, prescaled, q_null;      /* mode 2, as in qd_nearest_point_f32 (q_null: q == NULL)                */
+    int32_t fused_capacity;  /* blocks of the one-launch single-bucket kernel that are resident at once (256 on MI355X);     */
+                             /* 0: it may not be tried (qd_set_single_fused_mode(0), q aliases x, the stream is capturing)   */
+    int32_t cus;             /* compute units of the device (256 on MI355X)                                                  */
+    int64_t n, bucket;
+} QdTransformQuery;
+typedef struct QdPlannedLaunch {
+    char kernel[40];         /* as tools/launch_coverage.py spells it, e.g. "k_bucket_wave_any<0,5,1>"                       */
+    int32_t blocks, threads; /* grid and block size                                                                         */
+    int64_t lds_bytes;       /* dynamic LDS                                                                                 */
+} QdPlannedLaunch;
+typedef struct QdTransformPlan {
+    int64_t nb, row;         /* buckets, elements per bucket                                                                */
+    int64_t nvec;            /* k_bucket_vec: leading full buckets it takes (0 for every other kernel)                       */
+    int64_t m, nchunks;      /* k_bucket_chunk / k_bucket_chunk_any: buckets per chunk, whole chunks (0 otherwise)           */
+    int64_t nbk, amask;      /* k_bucket_wave_any: its buckets are [0, nbk); ~31 (0 otherwise)                               */
+    int32_t fine;            /* the kernel builds the fine cell table (k > 32, midpoint rule, no LDS staging of its own)     */
+    int32_t nlaunch;         /* launches, in order: 1 .. 3; 0: the call is refused (indices only, no pre-scaled stream)      */
+    QdPlannedLaunch launch[3];
+} QdTransformPlan;
+int qd_transform_plan(const QdTransformQuery* queries, int64_t count, QdTransformPlan* plans);
 
 /* mean_out[0] = mean(x) (float64 accumulation, one rounding).  Replaces tensor.mean(),
  * quant_functions.py:67. */

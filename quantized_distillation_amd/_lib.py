@@ -69,6 +69,23 @@ class QdHufCode(ctypes.Structure):
                 ('single', ctypes.c_int32), ('max_len', ctypes.c_int32)]
 
 
+class QdTransformQuery(ctypes.Structure):
+    """Mirror of `struct QdTransformQuery` in include/qd_hip.h."""
+    _fields_ = [(f, ctypes.c_int32) for f in ('mode', 'data_misalign', 'side_bytes', 'side_misalign', 'k', 'assign_mode', 'prescaled',
+                                              'q_null', 'fused_capacity', 'cus')] + [('n', ctypes.c_int64), ('bucket', ctypes.c_int64)]
+
+
+class QdPlannedLaunch(ctypes.Structure):
+    """Mirror of `struct QdPlannedLaunch` in include/qd_hip.h."""
+    _fields_ = [('kernel', ctypes.c_char * 40), ('blocks', ctypes.c_int32), ('threads', ctypes.c_int32), ('lds_bytes', ctypes.c_int64)]
+
+
+class QdTransformPlan(ctypes.Structure):
+    """Mirror of `struct QdTransformPlan` in include/qd_hip.h."""
+    _fields_ = [(f, ctypes.c_int64) for f in ('nb', 'row', 'nvec', 'm', 'nchunks', 'nbk', 'amask')] + \
+               [('fine', ctypes.c_int32), ('nlaunch', ctypes.c_int32), ('launch', QdPlannedLaunch * 3)]
+
+
 # symbol -> (restype, argtypes); every symbol declared in include/qd_hip.h must be listed here
 # (tests/test_abi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -79,6 +96,7 @@ SIGNATURES = {
     'qd_set_single_fused_mode': (c_int, [c_int]),
     'qd_num_buckets': (i64, [i64, i64]),
     'qd_padded_length': (i64, [i64, i64]),
+    'qd_transform_plan': (c_int, [c_p, i64, c_p]),         # tables of QdTransformQuery / QdTransformPlan (ctypes or numpy memory)
     'qd_mean_f32': (c_int, [c_f, i64, c_f, c_p, c_size, c_p]),
     'qd_uniform_f32': (c_int, [c_f, c_f, i64, i64, c_int, c_f, c_f, c_p, c_f, c_int, c_float, c_int, u64,
                                c_p, c_size, c_p]),

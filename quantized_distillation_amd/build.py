@@ -23,7 +23,8 @@ def hipcc():
 def _headers():
     """What every object / assembly file depends on besides its own source (ONE list for build_extension and
     device_assembly: qd_transform.h holds almost all kernel code)."""
-    return [os.path.join(_lib.CSRC, 'qd_common.h'), os.path.join(_lib.CSRC, 'qd_transform.h'), os.path.join(_lib.CSRC, 'qd_multi.h'),
+    return [os.path.join(_lib.CSRC, 'qd_common.h'), os.path.join(_lib.CSRC, 'qd_plan.h'), os.path.join(_lib.CSRC, 'qd_transform.h'),
+            os.path.join(_lib.CSRC, 'qd_multi.h'),
             os.path.join(_lib.INCLUDE, 'qd_hip.h'),
             os.path.abspath(__file__)]
 

@@ -13,6 +13,7 @@
 // Not a hot path (no driver reaches it): one wave per bucket, two passes, the second from L1/L2;
 // a whole-tensor bucket uses a two-stage reduction.
 #include "qd_common.h"
+#include "qd_plan.h"           // geometry()
 #include "../../include/qd_hip.h"
 
 using namespace qd;
@@ -129,11 +130,6 @@ __global__ __launch_bounds__(256) void k_abs_inverse(const float* u, const float
     }
 }
 
-inline void geometry(int64_t n, int64_t bucket, int64_t& nb, int64_t& row) {
-    if (bucket <= 0 || n < bucket) { nb = 1; row = n; return; }
-    row = bucket;
-    nb = (n + bucket - 1) / bucket;
-}
 inline int nblocks(int64_t items, int per) {
     int64_t b = (items + per - 1) / per;
     return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));

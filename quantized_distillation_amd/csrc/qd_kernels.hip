@@ -59,6 +59,46 @@ int64_t qd_padded_length(int64_t n, int64_t bucket) {
     return nb * row;
 }
 
+// The launcher's own decision, for inspection: the same plan_transform() on the same numbers (qd_plan.h), the kernel names
+// formatted from the family and arguments launch_planned switches on.  The one-launch kernel is "resident" when the caller's
+// capacity says so; the launcher asks the occupancy instead.
+int qd_transform_plan(const QdTransformQuery* queries, int64_t count, QdTransformPlan* plans) {
+    if (count < 0 || (count > 0 && (!queries || !plans))) return QD_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < count; ++i) {
+        const QdTransformQuery& q = queries[i];
+        if (q.mode < MODE_QDQ || q.mode > MODE_NEAREST || q.n < 1 || q.bucket < 0 || q.cus < 1) return QD_ERR_INVALID_ARGUMENT;
+    }
+    for (int64_t i = 0; i < count; ++i) {
+        const QdTransformQuery& q = queries[i];
+        PlanInput in = {};
+        in.mode = q.mode; in.n = q.n; in.bucket = q.bucket;
+        in.data_misalign = q.data_misalign; in.side_bytes = q.side_bytes; in.side_misalign = q.side_misalign;
+        in.k = q.k; in.assign_mode = q.assign_mode; in.prescaled = q.prescaled != 0; in.q_null = q.q_null != 0;
+        in.fused_ok = q.fused_capacity > 0;
+        in.cus = q.cus; in.grid_cap = kDefaultGridCap;
+        const TransformPlan pl = plan_transform(in);
+        QdTransformPlan& o = plans[i];
+        o = QdTransformPlan{};
+        o.nb = pl.nb; o.row = pl.row; o.nvec = pl.nvec; o.m = pl.m; o.nchunks = pl.nchunks; o.nbk = pl.nbk; o.amask = pl.amask;
+        o.fine = pl.fine; o.nlaunch = pl.nlaunch;
+        auto put = [&](int slot, const Launch& L) {
+            kernel_name(q.mode, L, o.launch[slot].kernel);
+            o.launch[slot].blocks = L.blocks; o.launch[slot].threads = L.threads; o.launch[slot].lds_bytes = (int64_t)L.lds;
+        };
+        bool fused = false;
+#define QD_PLAN_FUSED(I, V, W)                                                                                        \
+        if (!fused && pl.fused_blocks[I] > 0 && pl.fused_blocks[I] <= q.fused_capacity) {                             \
+            fused = true;                                                                                             \
+            o.nlaunch = 1;                                                                                            \
+            put(0, Launch{FAM_FUSED, V, W, 0, (int)pl.fused_blocks[I], 256, pl.fused_lds});                           \
+        }
+        QD_FUSED_SHAPES(QD_PLAN_FUSED)
+#undef QD_PLAN_FUSED
+        for (int j = 0; !fused && j < pl.nlaunch; ++j) put(j, pl.launch[j]);
+    }
+    return 0;
+}
+
 int qd_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int levels, float* alpha, float* beta,
                    uint8_t* level_idx, const float* mean, int clamp, float max_element, int stochastic,
                    uint64_t seed, void* workspace, size_t workspace_bytes, void* stream) {

@@ -17,7 +17,7 @@ namespace {
 // row like the vector kernel does) -- whatever the bucket size, from 4 elements up.  The bucket sizes of the vector kernel
 // (64 ... 2048, powers of two) stay there: same stream, no per-element bucket choice.
 // TWO = false: the bucket size is a multiple of 4, a float4 never straddles two buckets: one (alpha, beta) pair per float4.
-constexpr int kStreamU = 4;
+// (kStreamU = 4: qd_plan.h, which sizes the grid by it)
 template <bool TWO>
 __global__ __launch_bounds__(256) void k_nearest_prescaled_stream(KParams p) {
     PointStore Ts;
@@ -111,23 +111,8 @@ __global__ __launch_bounds__(256) void k_nearest_prescaled_stream(KParams p) {
     }
 }
 
-// true if the call was taken by the streaming kernel
-bool launch_prescaled_stream(KParams& p, int64_t bucket, hipStream_t st, int& rc) {
-    if (!p.prescaled || p.n < 4) return false;
-    geometry(p.n, bucket, p.nb, p.row);
-    if (p.row < 4) return false;
-    if (p.nb <= 1 && p.out) return false;          // one bucket: the single-bucket apply kernel already is a plain stream
-    if (((((uintptr_t)p.x) | ((uintptr_t)p.out)) & kDataAlign) != 0) return false;
-    if (p.idx && (p.idx_bytes == 8 ? (((uintptr_t)p.idx) & 15) != 0 : (((uintptr_t)p.idx) & 3) != 0)) return false;
-    const size_t tb = point_table_bytes(p.k, p.fine);
-    int blocks = blocks_for(p.n >> 2, 256 * kStreamU);                      // one 4 KiB tile per wave
-    const int cap = p.fine ? kFineBlocksPerCu * num_cus() : (1 << 30);
-    if (blocks > cap) blocks = cap;
-    if (p.row & 3) hipLaunchKernelGGL(k_nearest_prescaled_stream<true>, dim3(blocks), dim3(256), tb, st, p);
-    else hipLaunchKernelGGL(k_nearest_prescaled_stream<false>, dim3(blocks), dim3(256), tb, st, p);
-    rc = check_launch();
-    return true;
-}
+// (when the stream takes a call -- pre-scaled, n >= 4, buckets of 4 elements or more, more than one bucket or indices only,
+// aligned pointers -- is decided by plan_transform, qd_plan.h, and launched by launch_planned like every other family)
 
 }  // namespace
 
@@ -148,10 +133,8 @@ int qd_nearest_point_f32(const float* x, int prescaled, const float* points, int
     p.me = clamp ? max_element : INFINITY;
     p.idx = idx; p.idx_bytes = idx_bytes; p.pts = points; p.k = k; p.assign_mode = assign_mode;
     p.prescaled = prescaled ? 1 : 0;
-    p.fine = (k > 32 && assign_mode == QD_ASSIGN_MIDPOINT) ? 1 : 0;      // the fine cell table of qd_transform.h
-    int rc = 0;
-    if (n > 0 && launch_prescaled_stream(p, bucket, (hipStream_t)stream, rc)) return rc;
-    if (n > 0 && !q) return QD_ERR_INVALID_ARGUMENT;                          // (n < 4, a bucket below 4 elements, or a misaligned base)
+    // (indices only where the pre-scaled stream cannot take the call -- n < 4, a bucket below 4 elements, a misaligned base --
+    // has no plan: QD_ERR_INVALID_ARGUMENT)
     return run_transform<MODE_NEAREST>(p, bucket, workspace, workspace_bytes, (hipStream_t)stream);
 }
 

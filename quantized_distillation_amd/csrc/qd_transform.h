@@ -1,6 +1,7 @@
 // qd_transform.h -- the MODE-templated half of the gfx950 fake-quantization kernels: the per-element transforms, every
 // bucket kernel family (vector, chunk, chunk_any, one wave per bucket, lane groups, block per bucket), the single-bucket
-// kernels (three launches / one launch) and their launchers, ending in run_transform<MODE>().
+// kernels (three launches / one launch) and their launcher, run_transform<MODE>(): it derives the inputs of plan_transform()
+// (qd_plan.h: which kernel, which grid, which LDS -- one pure function), and launches what the plan says.
 //
 // Included by THREE translation units, one per mode, so that hipcc builds them in parallel (as one file the kernels took
 // 55 s to compile):
@@ -21,6 +22,7 @@
 #pragma once
 
 #include "qd_common.h"
+#include "qd_plan.h"       // the launch plan, and the constants the kernels share with it
 #include "../../include/qd_hip.h"
 
 #include <math.h>
@@ -35,11 +37,6 @@ using namespace qd;
 extern "C" __attribute__((visibility("hidden"))) int qd_fused_mode_state;
 
 namespace {
-
-enum Mode { MODE_QDQ = 0, MODE_SCALE = 1, MODE_NEAREST = 2 };
-
-constexpr int kMaxPoints = 1024;        // LDS table of quantization points
-constexpr int kPartialBlocks = 1024;    // stage-1 blocks of every two-stage reduction
 
 // Alignment the 16-byte (float4) global accesses of the single-tensor entry points need from their fp32 data pointers:
 // FOUR bytes.  global_load / global_store_dwordx4 take any dword-aligned address (the HSA queues run in unaligned access
@@ -74,9 +71,7 @@ struct KParams {
     int64_t nvec;        // number of leading full buckets handled by the vector path
 };
 
-// LDS-resident point table (+ midpoints, quant_functions.py:533)
-constexpr int kCells = 256;             // uniform grid over [0,1] that narrows the midpoint search (k > 32)
-
+// LDS-resident point table (+ midpoints, quant_functions.py:533; kCells, kFineCells, point_table_bytes: qd_plan.h)
 // The table lives at the START of the kernel's dynamic LDS (every nearest-point launch asks for point_table_bytes(k) more),
 // sized by the number of points: 256 bytes up to 32 points -- every configuration of the reference's scripts -- instead of
 // a static 10.3 KB for the 1024 points the ABI allows.  (The static table left the chunk kernels 6 / 5 blocks per CU, bound
@@ -95,7 +90,6 @@ struct PointStore {
     lds_u2* cell;                       // [kFineCells], `fine` only: {start | count << 16, first midpoint of the cell}
 };
 extern __shared__ __attribute__((aligned(16))) unsigned char qd_dyn_lds[];     // every kernel's dynamic LDS starts here
-constexpr int kSmallTable = 32;
 // Many points, midpoint rule (the per-step call): a FINE grid of 2048 cells over [0, 1] whose entry answers an element by
 // itself when its cell holds at most one midpoint -- index = start + (first midpoint <= u) -- with ONE 8-byte LDS read, no
 // loop; only cells with two or more midpoints fall back to the binary search inside the cell.  With k = 256 points spread
@@ -107,20 +101,7 @@ constexpr int kSmallTable = 32;
 // fallback: never slower than the narrowed search it replaces, only no faster.  16 KB more LDS, so only the kernels without
 // LDS staging of their own use it (`fine` is cleared for the chunk kernels), on a capped grid (kFineBlocksPerCu) so that
 // the table is built a few thousand times, not once per 16 KB of data.
-constexpr int kFineCells = 2048;
-// Grid cap of the kernels that build the fine table, in blocks per CU (6 are resident next to 26.6 KB of LDS).  Measured, K5
-// k = 256 at bucket 256 / 1000, 64 Mi elements (round 2's narrowed search: 117 / 144 us): 6 -> 102 / 110 us (every resident
-// block builds its table at the same moment, nothing to overlap it with), 12 -> 98 / 105, 24 -> 95 / 102, 48 -> 101 / 111,
-// uncapped (a table per 16 KB of data) -> 106 / 117.  (A compile-time constant; tools/ build variants of it for A/B runs.)
-#ifndef QD_FINE_BLOCKS_PER_CU
-#define QD_FINE_BLOCKS_PER_CU 24
-#endif
-constexpr int kFineBlocksPerCu = QD_FINE_BLOCKS_PER_CU;
-constexpr size_t kCoarseTableBytes = (size_t)2 * kMaxPoints * sizeof(float) + (size_t)2 * (kCells + 4) * sizeof(int);   // 10272
-__host__ __device__ constexpr size_t point_table_bytes(int k, int fine = 0) {
-    return k <= kSmallTable ? (size_t)2 * kSmallTable * sizeof(float)
-                            : kCoarseTableBytes + (fine ? (size_t)kFineCells * 8 : 0);
-}
+// (kFineCells = 2048; the cap kFineBlocksPerCu and its measurements: qd_plan.h)
 
 // What the kernels pass around: a handle on the LDS table.  (Tried in round 3 and dropped: for small point sets the points
 // and midpoints themselves in registers, the assignment as k - 1 compares and selects without any LDS access.  With k <= 8
@@ -676,7 +657,7 @@ __global__ __launch_bounds__(256) void k_bucket_vec(KParams p) {
     if (MODE == MODE_NEAREST) load_points(Tc, Ts, p.pts, p.k, p.fine);
 
     constexpr int BPW = (64 / LPB) * U;           // buckets per wave tile
-    constexpr int ROW = LPB * V * 4;              // elements per bucket
+    constexpr int ROW = LPB * V * 4;              // elements per bucket.  CONTRACT (plan_transform, held by tests/test_transform_plan.py): p.row == ROW
     const int lane = threadIdx.x & 63;
     const int sub = lane / LPB;                   // which lane group of the wave
     const int l = lane % LPB;                     // lane inside the bucket
@@ -758,6 +739,9 @@ void k_bucket_chunk(KParams p, int m, int64_t nchunks) {
     // dynamic LDS: [point table (nearest-point mode)] then per wave: pairs[VMAX * 64], ab[256], 1/alpha[256]
     float2* chunk_lds = (float2*)(qd_dyn_lds + (MODE == MODE_NEAREST ? point_table_bytes(p.k) : 0));
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // CONTRACT (plan_transform, held by tests/test_transform_plan.py for every bucket size): row % 4 == 0, 1 <= m <= 256 (ab, yt),
+    // m * row / 4 <= VMAX * 64 (pr, v[]), m < 64 -> m a power of two or 48 .. 63 (G below), nchunks == (n / row) / m, fine == 0,
+    // dynamic LDS == 2 * (VMAX * 64 + 256 + 128) * 8 + the coarse point table
     float2* pr = chunk_lds + w * (VMAX * 64 + 256 + 128);
     float2* ab = pr + VMAX * 64;
     float* yt = (float*)(ab + 256);
@@ -919,8 +903,8 @@ void k_bucket_chunk_any(KParams p, int m, int64_t nchunks, int lead) {
     // quantize + levels at bucket 33, 405 us for int64 point indices (docs/history/profiles/r03_side_outputs.txt).  (Up to 32 points: with
     // the 10.3 KB table of a larger point set the extra bytes cost a resident block, which measured slower than the scattered
     // stores: k = 256 at bucket 33: 316 us against 281 us.)
-    const bool stage8 = (MODE == MODE_QDQ && p.lev8 != nullptr) || (MODE == MODE_NEAREST && p.idx != nullptr && p.k <= 32);
-    const int wave_floats = VMAX * 256 + (stage8 ? VMAX * 64 : 0);
+    const bool stage8 = qd::stage8(MODE, p.lev8 != nullptr, p.idx != nullptr, p.k);
+    const int wave_floats = VMAX * 256 + (stage8 ? VMAX * 64 : 0);             // (the plan sizes the LDS by the same function)
     float* vals = (float*)chunk_lds + w * wave_floats;
     uint8_t* sidev = (uint8_t*)(vals + VMAX * 256);
 
@@ -948,7 +932,11 @@ void k_bucket_chunk_any(KParams p, int m, int64_t nchunks, int lead) {
         // Lane i of round j holds float4 (i + 64 j - h) of the chunk, h = the chunk's distance from the 128-byte line below
         // it: every load and store instruction then covers eight whole lines instead of straddling nine (chunks start at
         // arbitrary multiples of 16 bytes; measured on the one-wave-per-bucket kernel: 107.7 -> 100.1 us at bucket 1000).
-        // The launcher leaves room for the lead-in (nf + 7 <= VMAX * 64) or switches it off (lead = 0: sizes 506 .. 511).
+        // CONTRACT (plan_transform, held by tests/test_transform_plan.py for every bucket size): m % 4 == 0, m >= 4, room for the
+        // lead-in: m * row / 4 + 7 <= VMAX * 64, the lane rule of k_bucket_chunk, fine == 0, dynamic LDS == 2 * wave_floats * 4 +
+        // the coarse point table.  `lead` is always 1: the plan has no case without the lead-in (the host branch that passed 0,
+        // for sizes 506 .. 511, was unreachable and is gone); the parameter stays because removing it changes device code -- a
+        // later change, with an A/B measurement.
         const int h = lead ? (int)((e0 >> 2) & 7) : 0;
         {
             f4 v[VMAX];
@@ -1133,6 +1121,9 @@ void k_bucket_wave_any(KParams p, int64_t nbk, int64_t amask) {
         // no room for the rotation: the launcher keeps such buckets out of their range, block 0 does them with scalar
         // accesses below.)
         const bool tail_partial = V <= 16 && active && (((lo + row + 3) >> 2) << 2) > p.n;      // group-uniform
+        // CONTRACT (plan_transform, held by tests/test_transform_plan.py for every bucket size): nf <= 64 * G * V, that is
+        // row / 4 + (row % 4 ? 2 : 0) + (row % 32 ? 7 : 0) <= 64 * G * V; V <= 9 in the nearest-point mode (no scratch); nbk == nb
+        // for V <= 16, and for V > 16 only the leading buckets whose last float4 ends inside the tensor
         f4 v[V];
         float a = 1.0f, b = 0.0f;
         float mn = INFINITY, mx = -INFINITY;
@@ -1690,12 +1681,6 @@ bool carve(void* ws, size_t bytes, Workspace& w) {
     return true;
 }
 
-inline void geometry(int64_t n, int64_t bucket, int64_t& nb, int64_t& row) {
-    if (bucket <= 0 || n < bucket) { nb = 1; row = n; return; }
-    row = bucket;
-    nb = (n + bucket - 1) / bucket;
-}
-
 // compute units of the current device (256 on MI355X), cached PER DEVICE (qd_common.h)
 inline int num_cus() { return device_cus(); }
 
@@ -1708,185 +1693,46 @@ inline int grid_cap() {
     const int v = e ? atoi(e) : 0;
     if (v > 0) return v;
 #endif
-    return 1 << 20;
+    return kDefaultGridCap;
 }
-inline int blocks_for(int64_t items, int per_block) {
-    int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    const int cap = grid_cap();
-    return (int)(b < cap ? b : cap);
-}
+inline int blocks_for(int64_t items, int per_block) { return qd::blocks_for(items, per_block, grid_cap()); }
 
 inline int check_launch() {
     const hipError_t e = hipGetLastError();
     return (int)e;
 }
 
-// launch the bucketed transform for nb > 1 (or a short single bucket)
+// ---- the single-tensor transform: derive the plan's inputs, plan (qd_plan.h), launch what the plan says ------------------
+// The plan is a function of numbers: what needs a pointer or the runtime is turned into one here -- the alignment facts, the
+// compute-unit count (asked only in the nearest-point mode: nothing else caps a grid by it), and "the one-launch single-bucket
+// kernel may be tried" (not switched off by qd_set_single_fused_mode(0), not in place: a block that gives up re-reads x).
+// The plan's nb / row / nvec / fine enter the kernels' parameters here and nowhere else.
 template <int MODE>
-int launch_bucketed(KParams& p, hipStream_t st) {
-    const bool aligned = ((((uintptr_t)p.x) | ((uintptr_t)p.out)) & kDataAlign) == 0 &&
-                         (MODE != MODE_NEAREST || p.idx == nullptr || p.idx_bytes != 8 || (((uintptr_t)p.idx) & 15) == 0) &&
-                         (MODE != MODE_QDQ || p.lev8 == nullptr || (((uintptr_t)p.lev8) & 3) == 0);
-    const int64_t nfull = p.n / p.row;                 // leading full buckets
-    const size_t tb = MODE == MODE_NEAREST ? point_table_bytes(p.k, p.fine) : 0;      // dynamic LDS of every launch: the point table
-    // with the fine cell table the grid is capped (the kernels loop): the table is built once per resident block, not per tile
-    const int fine_cap = (MODE == MODE_NEAREST && p.fine) ? kFineBlocksPerCu * num_cus() : (1 << 30);
-    const size_t tbc = MODE == MODE_NEAREST ? point_table_bytes(p.k, 0) : 0;           // the chunk kernels': always the coarse table
-    // k_bucket_chunk_any stages level / point indices that fit a byte in LDS (the same expression as in the kernel)
-    const bool stage8 = (MODE == MODE_QDQ && p.lev8 != nullptr) || (MODE == MODE_NEAREST && p.idx != nullptr && p.k <= 32);
-#define QD_VEC(LPB, V, U)                                                                       \
-    {                                                                                           \
-        p.nvec = nfull;                                                                         \
-        constexpr int64_t bpw = (64 / LPB) * U;                                                 \
-        const int64_t tiles = (nfull + bpw - 1) / bpw;                                          \
-        int blocks = blocks_for(tiles, 4) + 1; /* +1: the block that owns the tail */           \
-        /* the vector kernel hides the narrowed search behind 7 waves per SIMD up to 64 points (99 us against 104 us with */ \
-        /* the fine table on a capped grid); the kernels with fewer resident waves gain from 33 points on */ \
-        if (MODE == MODE_NEAREST && p.k <= 64) p.fine = 0;                                      \
-        if (MODE == MODE_NEAREST && p.fine && blocks > fine_cap) blocks = fine_cap;             \
-        hipLaunchKernelGGL((k_bucket_vec<MODE, LPB, V, U>), dim3(blocks), dim3(256),            \
-                           MODE == MODE_NEAREST ? point_table_bytes(p.k, p.fine) : 0, st, p);   \
-        return check_launch();                                                                  \
-    }
-    if (aligned && p.nb > 1) {
-        switch (p.row) {
-            case 64: QD_VEC(16, 1, 4)
-            case 128: QD_VEC(16, 2, 2)
-            case 256: QD_VEC(16, 4, 1)
-            case 512: QD_VEC(64, 2, 2)
-            case 1024: QD_VEC(64, 4, 1)
-            case 2048: QD_VEC(64, 8, 1)
-            default: break;       // 4096, 8192: k_bucket_wave_any with two / four waves per bucket (8192: 91.2 vs 95.5 us as 32 float4 per lane)
-        }
-    }
-#undef QD_VEC
-    p.nvec = 0;
-    if (aligned && p.nb > 1 && p.row > 256 && p.row <= 32768) {
-        // one wave per bucket, any size (k_bucket_wave_any): sizes above 512, and sizes from 448 that are not a multiple of 4
-        // (multiples of 4 up to 512 stay with the chunk kernel: 300 -> 90 us against 127 us here; the vector sizes 512 /
-        // 1024 / 2048 were taken above).  The lane -> float4 mapping starts at the 128-byte line (32 elements) at or below
-        // the bucket (measured against 16- and 64-element boundaries: docs/history/profiles/r02_tune_kernels.txt).
-        const bool mult4 = (p.row & 3) == 0;
-        constexpr int al = 32;
-        const bool line_ok = (p.row * 4) % (al * 4) == 0;                        // every bucket starts on the boundary anyway
-        const int64_t amask = ~(int64_t)(al - 1);
-        // float4s a wave may have to hold: the bucket's own, +1 for a split first/last one, + the lead-in from the boundary
-        const int nf_max = (int)(p.row >> 2) + (mult4 ? 0 : 2) + (line_ok ? 0 : al / 4 - 1);
-        // every bucket, the short last one included (the float4 that would reach past the end of the tensor is fetched as
-        // x[n-4 .. n-1] and rotated: nothing outside the tensor is read, whatever the alignment of the base)
-        // (the two largest instances have no registers to spare for that and leave those buckets to block 0's scalar path)
-        int64_t nbk_all = p.nb, nbk_whole = p.nb;
-        while (nbk_whole > 0 && ((((nbk_whole * p.row < p.n ? nbk_whole * p.row : p.n) + 3) >> 2) << 2) > p.n) --nbk_whole;
-        if (nf_max <= 256 * 32 && (p.row > 512 || (!mult4 && p.row >= 448))) {
-#define QD_WAVE_ANY(V, G)                                                                                  \
-    {                                                                                                      \
-        const int64_t nbk = V > 16 ? nbk_whole : nbk_all;                                                  \
-        int blocks = blocks_for(nbk > 0 ? nbk : 1, 4 / G);                                                 \
-        if (blocks > fine_cap) blocks = fine_cap;                                                          \
-        hipLaunchKernelGGL((k_bucket_wave_any<MODE, V, G>), dim3(blocks), dim3(256), tb, st, p, nbk, amask); \
-        return check_launch();                                                                             \
-    }
-            // one wave per bucket up to 8 rounds (2048 elements), then two (up to 4096) and four waves per bucket
-            if constexpr (MODE == MODE_QDQ) {              // the hot mode: rounds in steps of one
-                if (nf_max <= 64 * 2) QD_WAVE_ANY(2, 1)
-                if (nf_max <= 64 * 3) QD_WAVE_ANY(3, 1)
-                if (nf_max <= 64 * 4) QD_WAVE_ANY(4, 1)
-                if (nf_max <= 64 * 5) QD_WAVE_ANY(5, 1)
-                if (nf_max <= 64 * 6) QD_WAVE_ANY(6, 1)
-                if (nf_max <= 64 * 7) QD_WAVE_ANY(7, 1)
-                if (nf_max <= 64 * 8) QD_WAVE_ANY(8, 1)
-                if (nf_max <= 128 * 5) QD_WAVE_ANY(5, 2)
-                if (nf_max <= 128 * 6) QD_WAVE_ANY(6, 2)
-                if (nf_max <= 128 * 7) QD_WAVE_ANY(7, 2)
-                if (nf_max <= 128 * 8) QD_WAVE_ANY(8, 2)
-                if (nf_max <= 256 * 5) QD_WAVE_ANY(5, 4)
-                if (nf_max <= 256 * 6) QD_WAVE_ANY(6, 4)
-                if (nf_max <= 256 * 7) QD_WAVE_ANY(7, 4)
-                if (nf_max <= 256 * 8) QD_WAVE_ANY(8, 4)
-                if (nf_max <= 256 * 9) QD_WAVE_ANY(9, 4)
-                // above 8192 elements: more float4s per lane again (8200 / 10000 / 16384 / 20000 took 148 / 182 / 155 / 284 us on
-                // the two-pass kernels below)
-                if (nf_max <= 256 * 12) QD_WAVE_ANY(12, 4)
-                if (nf_max <= 256 * 16) QD_WAVE_ANY(16, 4)
-                if (nf_max <= 256 * 24) QD_WAVE_ANY(24, 4)
-                QD_WAVE_ANY(32, 4)
-            } else {                                       // scale_down, nearest point: fewer instances
-                if (nf_max <= 64 * 3) QD_WAVE_ANY(3, 1)
-                if (nf_max <= 64 * 5) QD_WAVE_ANY(5, 1)
-                if (nf_max <= 64 * 8) QD_WAVE_ANY(8, 1)
-                if (nf_max <= 128 * 6) QD_WAVE_ANY(6, 2)
-                if (nf_max <= 128 * 8) QD_WAVE_ANY(8, 2)
-                if (nf_max <= 256 * 6) QD_WAVE_ANY(6, 4)
-                if (nf_max <= 256 * 9) QD_WAVE_ANY(9, 4)
-                // more float4s per lane: scale_down only -- the point search of the nearest-point mode keeps too much live
-                // and the compiler demotes the float4 array to scratch memory (272 / 528 bytes per lane); buckets above 9216
-                // elements take the two-pass kernels below in that mode
-                if constexpr (MODE == MODE_SCALE) {
-                    if (nf_max <= 256 * 16) QD_WAVE_ANY(16, 4)
-                    QD_WAVE_ANY(32, 4)
-                }
-            }
-#undef QD_WAVE_ANY
-        }
-    }
-    // float4 per lane a chunk holds.  Measured at 64 Mi elements, bucket 100 / 36 / 300 / 1000 / 2000 (the one-bucket-
-    // per-lane-group kernels below: 145 / 211 / 167 / 114 / 122 us): 16 -> 123 / 123 / 128 / 122 / 120 us (195 VGPRs,
-    // two waves per SIMD: the load and the compute phase of a wave do not overlap); 8 -> 100 / 100 / 103 / 108 / 108;
-    // 4 -> 124 / 131 / 130 / 118 / 121.  Bucket 12 / 4: 101 / 112 us instead of 571 / 1616.
-    constexpr int kChunkV = 8;
-    if (aligned && p.nb > 1 && (p.row & 3) == 0 && p.row <= (int64_t)kChunkV * 256) {
-        const int64_t bq = p.row >> 2;
-        // as many whole buckets as fit the chunk's kChunkV * 64 float4 (<= 256: the (alpha, beta) table), not the next power of
-        // two below it: bucket 36 fills 504 of the 512 float4 with m = 56 instead of 288 with m = 32.  Above 64 buckets a lane
-        // reduces whole buckets alone, below that 64 / m lanes share one, so m is then rounded down to a power of two.
-        int m = (int)((kChunkV * 64) / bq);
-        if (m > 256) m = 256;
-        if (m < 64) { int p2 = 1; while (p2 * 2 <= m) p2 *= 2; if (m < 48 || p2 == m) m = p2; else { /* 48..63 lanes, one bucket each */ } }
-        const int64_t nchunks = nfull / m;
-        if (nchunks > 0) {
-            const size_t lds = (size_t)2 * (kChunkV * 64 + 256 + 128) * sizeof(float2);   // two waves per block: pairs, (alpha, beta), 1/alpha
-            const int blocks = blocks_for(nchunks, 2) + 1;                             // +1: the block that owns the tail
-            p.fine = 0;                                                                // the chunk kernels stage data in LDS: coarse table
-            hipLaunchKernelGGL((k_bucket_chunk<MODE, kChunkV>), dim3(blocks), dim3(128), lds + tbc, st, p, m, nchunks);
-            return check_launch();
-        }
-    }
-    if (aligned && p.nb > 1 && (p.row & 3) != 0 && p.row * 4 <= (int64_t)kChunkV * 256) {
-        // a multiple of 4 (chunks start 16-byte aligned), as many buckets as fit kChunkV * 256 elements: bucket 33 fills
-        // 1980 of the 2048 elements with m = 60 instead of 1056 with m = 32
-        int m = (int)(((int64_t)kChunkV * 256 - 28) / p.row) & ~3;        // - 28 elements: the lead-in to the 128-byte line
-        const int lead = m >= 4;
-        if (!lead) m = 4;                                                  // 506 .. 511: four buckets fill the chunk, no lead-in
-        // (no upper limit on m: the kernel keeps no per-bucket table; bucket sizes 1, 2, 3, 5, 7 fill the chunk too.  Above 64
-        // buckets every lane reduces whole buckets alone: a multiple of 64 keeps all lanes busy in every round -- bucket 7:
-        // 102 us with m = 256, 107-110 us with m = 288)
-        if (m >= 64) m &= ~63;
-        if (m < 64) { int p2 = 4; while (p2 * 2 <= m) p2 *= 2; if (m < 48 || p2 == m) m = p2; }
-        const int64_t nchunks = nfull / m;
-        if (nchunks > 0) {
-            // two waves: the staged chunk, + a byte per element when level / point indices (<= 255) are asked for
-            const size_t lds = (size_t)2 * (kChunkV * 256 + (stage8 ? kChunkV * 64 : 0)) * sizeof(float);
-            const int blocks = blocks_for(nchunks, 2) + 1;
-            p.fine = 0;
-            hipLaunchKernelGGL((k_bucket_chunk_any<MODE, kChunkV>), dim3(blocks), dim3(128), lds + tbc, st, p, m, nchunks, lead);
-            return check_launch();
-        }
-    }
-    // (bucket sizes 513 .. 1023 that are not a multiple of 4 once had a 16-float4 instance of k_bucket_chunk_any here; since
-    // k_bucket_wave_any takes every size above 512 the branch was unreachable -- tools/launch_coverage.py -- and is gone)
-    if (p.row <= 256) {                                  // 16 buckets per block, a DPP row each
-        hipLaunchKernelGGL((k_bucket_groups<MODE, 16>), dim3(blocks_for(p.nb, 16) < fine_cap ? blocks_for(p.nb, 16) : fine_cap), dim3(256), tb, st, p);
-    } else if (p.row <= 16384) {                         // 4 buckets per block, one wave each
-        hipLaunchKernelGGL((k_bucket_groups<MODE, 64>), dim3(blocks_for(p.nb, 4) < fine_cap ? blocks_for(p.nb, 4) : fine_cap), dim3(256), tb, st, p);
-    } else {
-        hipLaunchKernelGGL((k_bucket_generic<MODE>), dim3(blocks_for(p.nb, 1) < fine_cap ? blocks_for(p.nb, 1) : fine_cap), dim3(1024), tb, st, p);
-    }
-    return check_launch();
+TransformPlan plan_call(KParams& p, int64_t bucket) {
+    PlanInput in = {};
+    in.mode = MODE;
+    in.n = p.n;
+    in.bucket = bucket;
+    in.data_misalign = (int)((((uintptr_t)p.x) | ((uintptr_t)p.out)) & 15);
+    const void* side = MODE == MODE_QDQ ? (const void*)p.lev8 : MODE == MODE_NEAREST ? (const void*)p.idx : nullptr;
+    in.side_bytes = !side ? 0 : MODE == MODE_QDQ ? 1 : p.idx_bytes;
+    in.side_misalign = (int)(((uintptr_t)side) & 15);
+    in.k = p.k;
+    in.assign_mode = p.assign_mode;
+    in.prescaled = MODE == MODE_NEAREST && p.prescaled;
+    in.q_null = MODE == MODE_NEAREST && p.out == nullptr;
+    in.fused_ok = qd_fused_mode_state != 0 && (const void*)p.x != (const void*)p.out;
+    in.cus = MODE == MODE_NEAREST ? num_cus() : 0;
+    in.grid_cap = grid_cap();
+    const TransformPlan pl = plan_transform(in);
+    p.nb = pl.nb;
+    p.row = pl.row;
+    p.nvec = pl.nvec;
+    p.fine = pl.fine;
+    return pl;
 }
 
 // one-launch single bucket (k_single_fused) when the tensor fits the register files of a resident grid
-constexpr int kNotFused = -1000;
 // qd_set_single_fused_mode(): 0 = always the three-launch path, 1 = default, 2 / 3 / 4 = every block / every block with
 // blockIdx % 7 == 3 / exactly one block skips the barrier and takes the give-up path, so that the tests reach the
 // contention fallback deterministically on an idle GPU.  A plain int: set it before launching, not concurrently.
@@ -1915,98 +1761,116 @@ int fused_capacity() {                                         // blocks of k_si
 }
 // one epoch sequence for ALL instantiations, 64 bits: a tag never repeats on a slot set (epoch 0 = a never-written slot)
 std::atomic<uint64_t> next_launch{1};
-// Measured on MI355X (docs/history/profiles/r02_k1g_fused.txt): a device-scope round trip costs 1.5-2 us, so the barrier adds ~3.5 us
-// to a kernel -- about what a kernel boundary costs -- and the load and store phases of the register-resident kernel do
-// not overlap, while the three-launch path's second read is served by the 256 MiB Infinity Cache.  One launch wins only
-// where the call is launch-bound: up to 1 Mi elements (GPU time 7.8 vs 9.7 us at 0.1 M, 10.8 vs 10.9 at 0.8 M; one host
-// launch instead of two); at 2.8 M / 5.3 M elements it measured 22 / 21 us against 16 / 17.5 us.
-constexpr int64_t kFusedMaxN = (int64_t)1 << 20;
-template <int MODE>
-int launch_single_fused(KParams& p, hipStream_t st) {
-    const int fmode = qd_fused_mode_state;
-    if (fmode == 0 || ((((uintptr_t)p.x) | ((uintptr_t)p.out)) & kDataAlign) != 0) return kNotFused;
-    if ((const void*)p.x == (const void*)p.out) return kNotFused;   // in place: a block that gives up re-reads x
-    // a captured launch would bake its barrier slot and epoch into the graph, and two replays in flight would share them
+template <int MODE, int V, int W>
+void launch_fused(const KParams& p, int64_t blocks, size_t lds, int fmode, hipStream_t st) {
+    uint64_t epoch;
+    unsigned tag_min, tag_max;
+    do {                                                       // both tags non-zero: 0 | 0 is a never-written slot
+        epoch = next_launch.fetch_add(1, std::memory_order_relaxed);
+        tag_min = (unsigned)epoch;
+        tag_max = tag_min ^ ((unsigned)(epoch >> 32) * 0x9E3779B9u);
+    } while (tag_min == 0u || tag_max == 0u);
+    const int slot = (int)(epoch % kFusedSlots);
+    hipLaunchKernelGGL((k_single_fused<MODE, V, W>), dim3((unsigned)blocks), dim3(256), lds, st, p, slot, tag_min, tag_max,
+                       fmode >= 2 ? fmode - 1 : 0);
+}
+// a captured launch would bake its barrier slot and epoch into the graph, and two replays in flight would share them
+inline bool stream_capturing(hipStream_t st) {
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap_status) != hipSuccess || cap_status != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return kNotFused;
-    }
-    if (MODE == MODE_NEAREST && p.idx && p.idx_bytes == 8 && (((uintptr_t)p.idx) & 15)) return kNotFused;
-    if (MODE == MODE_QDQ && p.lev8 && (((uintptr_t)p.lev8) & 3)) return kNotFused;
-    if (p.n > kFusedMaxN) return kNotFused;
-    const int64_t n4 = p.n >> 2;
-    const int64_t lanes = (n4 + 255) / 256;                    // blocks needed at one float4 per lane
-#define QD_FUSED(V, W)                                                                                     \
-    {                                                                                                      \
-        const int cap = fused_capacity<MODE, V, W>();                                                      \
-        const int64_t blocks = (lanes + V - 1) / V;                                                        \
-        if (cap > 0 && blocks <= cap) {                                                                    \
-            uint64_t epoch;                                                                                \
-            unsigned tag_min, tag_max;                                                                     \
-            do {                                            /* both tags non-zero: 0 | 0 is a never-written slot */ \
-                epoch = next_launch.fetch_add(1, std::memory_order_relaxed);                               \
-                tag_min = (unsigned)epoch;                                                                 \
-                tag_max = tag_min ^ ((unsigned)(epoch >> 32) * 0x9E3779B9u);                               \
-            } while (tag_min == 0u || tag_max == 0u);                                                      \
-            const int slot = (int)(epoch % kFusedSlots);                                                   \
-            p.nvec = 0;                                                                                    \
-            hipLaunchKernelGGL((k_single_fused<MODE, V, W>), dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), \
-                               MODE == MODE_NEAREST ? point_table_bytes(p.k, p.fine) : 0, st, p, \
-                               slot, tag_min, tag_max, fmode >= 2 ? fmode - 1 : 0);          \
-            return check_launch();                                                                         \
-        }                                                                                                  \
-    }
-    QD_FUSED(1, 4) QD_FUSED(4, 4)
-#undef QD_FUSED
-    return kNotFused;
+    if (hipStreamIsCapturing(st, &cap_status) == hipSuccess && cap_status == hipStreamCaptureStatusNone) return false;
+    (void)hipGetLastError();
+    return true;
 }
 
-// single bucket spanning a large tensor: one fused launch when it fits on chip, else reduce -> finalize -> apply
+// (defined in qd_nearest.hip: planned and launched in the nearest-point mode only.  The launch bounds must stand on this first
+// declaration: the definition's alone are ignored -- tools/device_code_diff.py showed the kernel compiled for 1024 threads)
+template <bool TWO>
+__global__ __launch_bounds__(256) void k_nearest_prescaled_stream(KParams p);
+
+// One launch of a plan: the kernel its family and arguments name, instantiated from the same lists the plan selected from
+// (qd_plan.h), with the grid, block and dynamic LDS the plan computed.
 template <int MODE>
-int launch_single(KParams& p, void* ws, size_t ws_bytes, hipStream_t st) {
-    constexpr int64_t kSmall = 16384;
-    if (p.n <= kSmall) {                               // one block does both passes, one launch
-        p.nvec = 0;
-        hipLaunchKernelGGL((k_bucket_generic<MODE>), dim3(1), dim3(1024), MODE == MODE_NEAREST ? point_table_bytes(p.k, p.fine) : 0, st, p);
-        return check_launch();
+void launch_planned(const Launch& L, const TransformPlan& pl, const KParams& p, const Workspace& w, hipStream_t st) {
+    const dim3 grid((unsigned)L.blocks), block((unsigned)L.threads);
+    const float* ab = pl.ab_ready ? w.ab : nullptr;             // k_single_apply: (alpha, beta) in the scratch slot, or nparts partials to fold
+    switch (L.family) {
+        case FAM_VEC:
+#define QD_LAUNCH_VEC(ROW, LPB, V, U) \
+            if (L.a == LPB && L.b == V) hipLaunchKernelGGL((k_bucket_vec<MODE, LPB, V, U>), grid, block, L.lds, st, p);
+            QD_VEC_SHAPES(QD_LAUNCH_VEC)
+#undef QD_LAUNCH_VEC
+            break;
+        case FAM_WAVE_ANY:
+#define QD_LAUNCH_WAVE(V, G) \
+            if (L.a == V && L.b == G) hipLaunchKernelGGL((k_bucket_wave_any<MODE, V, G>), grid, block, L.lds, st, p, pl.nbk, pl.amask);
+            if constexpr (MODE == MODE_QDQ) { QD_WAVE_SHAPES_QDQ(QD_LAUNCH_WAVE) }
+            else if constexpr (MODE == MODE_SCALE) { QD_WAVE_SHAPES_SCALE(QD_LAUNCH_WAVE) }
+            else { QD_WAVE_SHAPES_NEAREST(QD_LAUNCH_WAVE) }
+#undef QD_LAUNCH_WAVE
+            break;
+        case FAM_CHUNK:
+            hipLaunchKernelGGL((k_bucket_chunk<MODE, kChunkV>), grid, block, L.lds, st, p, pl.m, pl.nchunks);
+            break;
+        case FAM_CHUNK_ANY:                                     // lead = 1: the plan has no case without the lead-in
+            hipLaunchKernelGGL((k_bucket_chunk_any<MODE, kChunkV>), grid, block, L.lds, st, p, pl.m, pl.nchunks, 1);
+            break;
+        case FAM_GROUPS:
+            if (L.a == 16) hipLaunchKernelGGL((k_bucket_groups<MODE, 16>), grid, block, L.lds, st, p);
+            else hipLaunchKernelGGL((k_bucket_groups<MODE, 64>), grid, block, L.lds, st, p);
+            break;
+        case FAM_GENERIC:
+            hipLaunchKernelGGL((k_bucket_generic<MODE>), grid, block, L.lds, st, p);
+            break;
+        case FAM_MINMAX_PARTIAL:
+            hipLaunchKernelGGL(k_minmax_partial, grid, block, 0, st, p.x, p.n, p.mean, p.me, w.minmax_part);
+            break;
+        case FAM_MINMAX_FINAL:
+            hipLaunchKernelGGL(k_minmax_final, grid, block, 0, st, w.minmax_part, pl.nparts, w.ab, p.alpha, p.beta);
+            break;
+        case FAM_SINGLE_APPLY:
+            hipLaunchKernelGGL((k_single_apply<MODE>), grid, block, L.lds, st, p, ab, w.minmax_part, pl.nparts);
+            break;
+        case FAM_PRESCALED_STREAM:
+            if constexpr (MODE == MODE_NEAREST) {
+                if (L.a) hipLaunchKernelGGL(k_nearest_prescaled_stream<true>, grid, block, L.lds, st, p);
+                else hipLaunchKernelGGL(k_nearest_prescaled_stream<false>, grid, block, L.lds, st, p);
+            }
+            break;
+        default: break;                                        // (FAM_FUSED needs the occupancy: apply_plan)
     }
-    Workspace w;
-    if (!carve(ws, ws_bytes, w)) return QD_ERR_WORKSPACE_TOO_SMALL;
-    if (!(MODE == MODE_NEAREST && p.prescaled)) {
-        const int rc = launch_single_fused<MODE>(p, st);
-        if (rc != kNotFused) return rc;
+}
+
+template <int MODE>
+int apply_plan(const TransformPlan& pl, const KParams& p, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (pl.nlaunch == 0) return QD_ERR_INVALID_ARGUMENT;        // indices only, and the pre-scaled stream cannot take the call
+    Workspace w = {};
+    if (pl.needs_workspace && !carve(ws, ws_bytes, w)) return QD_ERR_WORKSPACE_TOO_SMALL;
+    if (pl.fused_blocks[0] > 0 && !stream_capturing(st)) {      // one launch, if that many blocks are resident at once
+        const int fmode = qd_fused_mode_state;
+        bool fused = false;
+#define QD_TRY_FUSED(I, V, W)                                                                                         \
+        if (!fused) {                                                                                                 \
+            const int cap = fused_capacity<MODE, V, W>();                                                             \
+            fused = cap > 0 && pl.fused_blocks[I] <= cap;                                                             \
+            if (fused) launch_fused<MODE, V, W>(p, pl.fused_blocks[I], pl.fused_lds, fmode, st);                      \
+        }
+        QD_FUSED_SHAPES(QD_TRY_FUSED)
+#undef QD_TRY_FUSED
+        if (fused) return check_launch();
     }
-    const float* ab = nullptr;
-    int nparts = 0;
-    if (MODE == MODE_NEAREST && p.prescaled) {
-        // alpha/beta are inputs: copy the pair into the scratch slot the apply kernel reads
+    if (pl.copies_ab) {            // alpha/beta are inputs: copy the pair into the scratch slot the apply kernel reads
         (void)hipMemcpyAsync(w.ab, p.alpha, sizeof(float), hipMemcpyDeviceToDevice, st);
         (void)hipMemcpyAsync(w.ab + 1, p.beta, sizeof(float), hipMemcpyDeviceToDevice, st);
-        ab = w.ab;
-    } else {
-        int pb = blocks_for(p.n, 256 * 4 * 8);
-        if (pb > kPartialBlocks) pb = kPartialBlocks;
-        hipLaunchKernelGGL(k_minmax_partial, dim3(pb), dim3(256), 0, st, p.x, p.n, p.mean, p.me, w.minmax_part);
-        nparts = pb;
-        if (p.n > ((int64_t)8 << 20)) {      // > 32 MB: thousands of apply blocks, fold once in its own launch
-            hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(256), 0, st, w.minmax_part, pb, w.ab, p.alpha, p.beta);
-            ab = w.ab;
-        }
     }
-    const int blocks = blocks_for(p.n, 256 * 4 * 4);
-    hipLaunchKernelGGL((k_single_apply<MODE>), dim3(blocks < ((MODE == MODE_NEAREST && p.fine) ? kFineBlocksPerCu * num_cus() : (1 << 30)) ? blocks : kFineBlocksPerCu * num_cus()), dim3(256),
-                       MODE == MODE_NEAREST ? point_table_bytes(p.k, p.fine) : 0, st, p, ab,
-                       w.minmax_part, nparts);
+    for (int i = 0; i < pl.nlaunch; ++i) launch_planned<MODE>(pl.launch[i], pl, p, w, st);
     return check_launch();
 }
 
 template <int MODE>
 int run_transform(KParams& p, int64_t bucket, void* ws, size_t ws_bytes, hipStream_t st) {
     if (p.n == 0) return 0;
-    geometry(p.n, bucket, p.nb, p.row);
-    if (p.nb == 1) return launch_single<MODE>(p, ws, ws_bytes, st);
-    return launch_bucketed<MODE>(p, st);
+    const TransformPlan pl = plan_call<MODE>(p, bucket);
+    return apply_plan<MODE>(pl, p, ws, ws_bytes, st);
 }
 
 }  // namespace

@@ -16,8 +16,8 @@ What the header promises and no value comparison through the Python API can see:
 A Case is ONE call: the entry point, its arguments in the header's order (scalars, Ref(name) of a placed array, None, WS /
 WSB / STREAM) and `expect`, the reference of every written array -- oracle/oracle_c.py and oracle/oracle_np.py, the functions
 the parity suite compares with, plain numpy where the oracle has none.  A Group is the list of cases that reach one path of
-one launcher (csrc/qd_transform.h: launch_bucketed, launch_single; the thresholds are restated next to each group so that a
-reader can check them); the two test files parametrise over groups.  Everything is compared bit for bit; the K6 sums go
+one launcher (csrc/qd_plan.h: plan_transform; every group names the kernel(s) it reaches, and tests/test_transform_plan.py
+holds the plan to that); the two test files parametrise over groups.  Everything is compared bit for bit; the K6 sums go
 through errlog.check_sum (their three runs must still agree bit for bit)."""
 import collections
 import math
@@ -394,7 +394,7 @@ def k1(tag, x, bucket, levels=16, px=0, pq=4, ps=12, alias=False, want_ab=True, 
 
 
 def _single_ws(n, bucket):
-    """launch_single carves the workspace for one bucket of more than 16384 elements (csrc/qd_transform.h: kSmall)."""
+    """The launcher carves the workspace for one bucket of more than 16384 elements (csrc/qd_plan.h: kSingleSmallN)."""
     return nbuckets(n, bucket) == 1 and n > 16384
 
 
@@ -482,34 +482,57 @@ def k4(tag, x, bucket, k=16, mode=0, idx_bytes=8, prescaled=0, px=0, pq=4, ps=12
 
 
 # ---------------------------------------------------------------- the launcher paths of K1 / K2 / K4 (run_transform)
-# (bucket, full buckets, path): launch_bucketed of csrc/qd_transform.h with 4-byte aligned x / out
+class Path(str):
+    """The explanatory text of a launcher path, and as data the kernel(s) it names: `kernels` is what qd_transform_plan must
+    return for every case of the group, for K1 / K2 / K4 (mode 0 / 1 / 2) -- one pattern with %d for the mode, or one per mode;
+    ' ; ' separates the launches of a sequence.  tests/test_transform_plan.py holds the plan to it; the text is for the reader."""
+
+    def __new__(cls, kernels, text):
+        self = str.__new__(cls, text)
+        self.kernels = kernels
+        return self
+
+    def kernels_of(self, mode):
+        pat = self.kernels if isinstance(self.kernels, str) else self.kernels[mode]
+        return [k.replace('%d', str(mode)) for k in pat.split(' ; ')]
+
+
+# (bucket, full buckets, path): plan_transform of csrc/qd_plan.h with 4-byte aligned x / out
 BUCKET_PATHS = [
-    (64, 10, 'k_bucket_vec<16,1,4>: 16 buckets per wave tile, ten buckets = one partial tile + the tail block'),
-    (128, 10, 'k_bucket_vec<16,2,2>'),
-    (256, 10, 'k_bucket_vec<16,4,1>'),
-    (512, 10, 'k_bucket_vec<64,2,2>'),
-    (1024, 10, 'k_bucket_vec<64,4,1>'),
-    (2048, 10, 'k_bucket_vec<64,8,1>'),
-    (100, 21, 'k_bucket_chunk: bq = 25 float4, m = 16 buckets per chunk: one whole chunk + 5 leftover full buckets'),
-    (36, 61, 'k_bucket_chunk: bq = 9, m = 56 (48 .. 63 lanes, one bucket each): one chunk + 5 buckets'),
-    (33, 65, 'k_bucket_chunk_any: m = 60 buckets per chunk with the lead-in: one chunk + 5 buckets'),
-    (7, 261, 'k_bucket_chunk_any: m = 256 (a lane reduces whole buckets alone): one chunk + 5 buckets'),
-    (447, 6, 'k_bucket_chunk_any: the largest bucket it takes (257 .. 447, no multiple of 4: m = 4 with the lead-in): one chunk + 2 buckets'),
-    (509, 6, 'k_bucket_wave_any (nf_max = 127 + 2 + 7), NOT the m < 4 branch of k_bucket_chunk_any it was written for: sizes from 448 that '
-             'are no multiple of 4 return from the wave kernel first, so that branch is dead (DESIGN.md, findings)'),
-    (449, 6, 'k_bucket_wave_any: not a multiple of 4, >= 448: nf_max = 112 + 2 + 7'),
-    (513, 6, 'k_bucket_wave_any: the first size above 512'),
-    (1000, 6, 'k_bucket_wave_any: a multiple of 4 that is no multiple of 32 (lead-in from the 128-byte line)'),
-    (4097, 5, 'k_bucket_wave_any: four waves per bucket (nf_max = 1024 + 2 + 7 = 1033: K1 V = 5, K2 / K4 V = 6, G = 4), odd size'),
-    (20000, 3, 'k_bucket_wave_any V > 16 (K1: 24, K2: 32; K4: k_bucket_generic): the short last bucket goes to block 0'),
-    (100, 3, 'k_bucket_groups<16>: bucket <= 256 with fewer full buckets (3) than a chunk holds (16)'),
-    (300, 3, 'k_bucket_groups<64>: 257 .. 16384 (bq = 75, m = 4) with 3 full buckets'),
-    (40000, 2, 'k_bucket_generic: a bucket above 32768'),
+    (64, 10, Path('k_bucket_vec<%d,16,1,4>', 'k_bucket_vec<16,1,4>: 16 buckets per wave tile, ten buckets = one partial tile + the tail block')),
+    (128, 10, Path('k_bucket_vec<%d,16,2,2>', 'k_bucket_vec<16,2,2>')),
+    (256, 10, Path('k_bucket_vec<%d,16,4,1>', 'k_bucket_vec<16,4,1>')),
+    (512, 10, Path('k_bucket_vec<%d,64,2,2>', 'k_bucket_vec<64,2,2>')),
+    (1024, 10, Path('k_bucket_vec<%d,64,4,1>', 'k_bucket_vec<64,4,1>')),
+    (2048, 10, Path('k_bucket_vec<%d,64,8,1>', 'k_bucket_vec<64,8,1>')),
+    (100, 21, Path('k_bucket_chunk<%d,8>', 'k_bucket_chunk: bq = 25 float4, m = 16 buckets per chunk: one whole chunk + 5 leftover full buckets')),
+    (36, 61, Path('k_bucket_chunk<%d,8>', 'k_bucket_chunk: bq = 9, m = 56 (48 .. 63 lanes, one bucket each): one chunk + 5 buckets')),
+    (33, 65, Path('k_bucket_chunk_any<%d,8>', 'k_bucket_chunk_any: m = 60 buckets per chunk with the lead-in: one chunk + 5 buckets')),
+    (7, 261, Path('k_bucket_chunk_any<%d,8>', 'k_bucket_chunk_any: m = 256 (a lane reduces whole buckets alone): one chunk + 5 buckets')),
+    (447, 6, Path('k_bucket_chunk_any<%d,8>',
+                  'k_bucket_chunk_any: the largest bucket it takes (257 .. 447, no multiple of 4: m = 4 with the lead-in): one chunk + 2 buckets')),
+    (509, 6, Path('k_bucket_wave_any<%d,3,1>',
+                  'k_bucket_wave_any (nf_max = 127 + 2 + 7): sizes from 448 that are no multiple of 4 return from the wave kernel first, so the '
+                  'm < 4 branch of k_bucket_chunk_any once written for 506 .. 511 was dead and is gone (DESIGN.md, findings)')),
+    (449, 6, Path(('k_bucket_wave_any<%d,2,1>', 'k_bucket_wave_any<%d,3,1>', 'k_bucket_wave_any<%d,3,1>'),
+                  'k_bucket_wave_any: not a multiple of 4, >= 448: nf_max = 112 + 2 + 7')),
+    (513, 6, Path('k_bucket_wave_any<%d,3,1>', 'k_bucket_wave_any: the first size above 512')),
+    (1000, 6, Path('k_bucket_wave_any<%d,5,1>', 'k_bucket_wave_any: a multiple of 4 that is no multiple of 32 (lead-in from the 128-byte line)')),
+    (4097, 5, Path(('k_bucket_wave_any<%d,5,4>', 'k_bucket_wave_any<%d,6,4>', 'k_bucket_wave_any<%d,6,4>'),
+                   'k_bucket_wave_any: four waves per bucket (nf_max = 1024 + 2 + 7 = 1033: K1 V = 5, K2 / K4 V = 6, G = 4), odd size')),
+    (20000, 3, Path(('k_bucket_wave_any<%d,24,4>', 'k_bucket_wave_any<%d,32,4>', 'k_bucket_generic<%d>'),
+                    'k_bucket_wave_any V > 16 (K1: 24, K2: 32; K4: k_bucket_generic): the short last bucket goes to block 0')),
+    (100, 3, Path('k_bucket_groups<%d,16>', 'k_bucket_groups<16>: bucket <= 256 with fewer full buckets (3) than a chunk holds (16)')),
+    (300, 3, Path('k_bucket_groups<%d,64>', 'k_bucket_groups<64>: 257 .. 16384 (bq = 75, m = 4) with 3 full buckets')),
+    (40000, 2, Path('k_bucket_generic<%d>', 'k_bucket_generic: a bucket above 32768')),
 ]
-SINGLE_SMALL = [(1000, 'k_bucket_generic, one block'), (16384, 'k_bucket_generic, one block: the largest'),
-                (16385, 'k_single_fused<V = 1>: the smallest tensor that takes the workspace')]
-SINGLE_LARGE = [(300001, 'k_single_fused<V = 4>'), ((1 << 20) + 3, 'k_minmax_partial + k_single_apply (above kFusedMaxN)'),
-                ((8 << 20) + 5, 'k_minmax_partial + k_minmax_final + k_single_apply (above 8 Mi elements)')]
+SINGLE_SMALL = [(1000, Path('k_bucket_generic<%d>', 'k_bucket_generic, one block')),
+                (16384, Path('k_bucket_generic<%d>', 'k_bucket_generic, one block: the largest')),
+                (16385, Path('k_single_fused<%d,1,4>', 'k_single_fused<V = 1>: the smallest tensor that takes the workspace'))]
+SINGLE_LARGE = [(300001, Path('k_single_fused<%d,4,4>', 'k_single_fused<V = 4>')),
+                ((1 << 20) + 3, Path('k_minmax_partial ; k_single_apply<%d>', 'k_minmax_partial + k_single_apply (above kFusedMaxN)')),
+                ((8 << 20) + 5, Path('k_minmax_partial ; k_minmax_final ; k_single_apply<%d>',
+                                     'k_minmax_partial + k_minmax_final + k_single_apply (above 8 Mi elements)'))]
 FUSED_MODES = [(0, 'three launches'), (2, 'every block gives up'), (3, 'blocks with blockIdx % 7 == 3 give up'), (4, 'one block gives up')]
 
 

@@ -59,7 +59,7 @@ def test_every_compute_entry_point_checks_its_arguments_before_touching_the_devi
     GPU), the way the reference's functions raise ValueError before any work (quant_functions.py:22-33,230-236)."""
     import ctypes
     host_only = {'qd_abi_version', 'qd_target_arch', 'qd_error_string', 'qd_workspace_bytes', 'qd_set_single_fused_mode', 'qd_num_buckets',
-                 'qd_padded_length', 'qd_multi_plan', 'qd_multi_global_plan', 'qd_multi_dq_plan', 'qd_packed_bytes',
+                 'qd_padded_length', 'qd_transform_plan', 'qd_multi_plan', 'qd_multi_global_plan', 'qd_multi_dq_plan', 'qd_packed_bytes',
                  'qd_order_stats_workspace_bytes'}
     checked = 0
     for name, (res, args) in sorted(_lib.SIGNATURES.items()):

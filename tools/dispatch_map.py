@@ -10,7 +10,13 @@ the markers.
     python tools/dispatch_map.py --trace      on the GPU box: runs itself under rocprofv3, writes gpurun_out/dispatch_map.txt
     python tools/dispatch_map.py --calls      (child) issues the calls, writes the labels to $QD_DISPATCH_LABELS
 
-The table goes to profiles/rNN_dispatch_map.txt; tools/launch_coverage.py says which instantiations the TESTS reach.
+The table goes to profiles/dispatch_map.txt; tools/launch_coverage.py says which instantiations the TESTS reach.
+
+Look first at qd_transform_plan (include/qd_hip.h): for the single-tensor transform -- qd_uniform_f32, qd_scale_down_f32,
+qd_nearest_point_f32 -- the launcher's decision is one pure function (csrc/qd_plan.h) that the library exports, so the kernel
+of ANY geometry can be asked on a machine without a GPU, and tests/test_transform_plan.py sweeps it over every bucket size.
+This trace is the ground truth that test holds the plan to (its uniformQuantization, scale_down, nonUniformQuantization and
+diff-quant forward rows: keep their labels parseable), and the only map of the launchers that have no plan entry point.
 """
 import csv
 import glob
