@@ -495,8 +495,9 @@ int qd_huffman_decode_f32(const uint32_t* words, int64_t nwords, const uint32_t*
 /* ---- order statistics for initialize_quantization_points (quantization/help_functions.py:140-154: the reference
  * copies the scaled tensor to the host and calls np.percentile(a, linspace(0, 100, k)), which needs the two
  * neighbouring order statistics of each of the k virtual indices).
- * qd_order_stats_f32: out[t] (device, m floats) = the ranks[t]-th smallest element of x[0..n) (0-based; NaNs order
- *   last, -0 before +0), found by a 12|10|10-bit radix SELECT: x is read three times and never sorted or modified.
+ * qd_order_stats_f32: out[t] (device, m floats) = the ranks[t]-th smallest element of x[0..n) (0-based; every NaN, with
+ *   either sign bit and any payload, orders last -- after +inf -- and a rank among the NaNs returns a NaN, not the bits of
+ *   a particular one; -0 before +0), found by a 12|10|10-bit radix SELECT: x is read three times and never sorted or modified.
  *   ranks is a HOST array of m non-decreasing values in [0, n); 1 <= m <= QD_ORDER_STATS_MAX_RANKS; n < 2^32
  *   (QD_ERR_UNSUPPORTED beyond either).  workspace: qd_order_stats_workspace_bytes(m) bytes of device memory. */
 #define QD_ORDER_STATS_MAX_RANKS 32

@@ -12,8 +12,10 @@
 //
 // Three reads of the array (4 B/elem each), nothing written but per-block partial histograms (summed by the picking
 // kernels: no global atomics, no zeroing launch, deterministic).  The counters of passes 2 and 3 are [targets][1024] in
-// LDS (<= 32 targets = 128 KiB of the 160 KiB), one 1024-lane block per CU.  Exact for every float (NaNs order last,
-// -0 before +0); equal keys are the same value, so ties need no care.
+// LDS (<= 32 targets = 128 KiB of the 160 KiB), one 1024-lane block per CU.  Exact for every float; every NaN -- either
+// sign bit, any payload -- takes the one largest key, so all NaNs order last, after +inf, as in np.sort and np.partition, and a
+// rank among them returns a NaN (not the bits of a particular one).  -0 orders before +0; equal keys are the same value,
+// so ties need no care.
 #include "qd_common.h"
 #include <atomic>
 
@@ -35,8 +37,12 @@ struct Ranks {
 
 __device__ __forceinline__ uint32_t order_key(float v) {
     const uint32_t b = __float_as_uint(v);
+    // every NaN, whatever its sign bit or payload, takes the one key above +inf's (0xFF800000); without this a NaN with
+    // the sign bit set (0xFFC00000, what 0/0 and inf - inf give on x86) would get a key below -inf's and order FIRST
+    if ((b << 1) > 0xFF000000u) return 0xFFFFFFFFu;
     return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
 }
+// key_value(0xFFFFFFFF) = 0x7FFFFFFF, a NaN: a rank among the NaNs returns a NaN
 __device__ __forceinline__ float key_value(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }

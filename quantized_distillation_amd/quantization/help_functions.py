@@ -138,7 +138,9 @@ def order_statistics(values, ranks):
     """values[...] sorted ascending, at the (numpy int64, any order, repeats allowed) 0-based `ranks` -- as a float32
     numpy array, without sorting: a 12|10|10-bit radix select on the device (qd_order_stats_f32, csrc/qd_select.hip)
     reads `values` three times per 32 distinct ranks and only the selected values leave the device.  More than
-    2 * 32 distinct ranks (num_points > 32): one device sort and a gather instead."""
+    2 * 32 distinct ranks (num_points > 32): one device sort and a gather instead.  On all three paths (np.partition for a
+    CPU tensor, the select, the sort) every NaN -- either sign bit, any payload -- orders last, after +inf, and a rank among
+    the NaNs returns a NaN (tests/select_cases.py)."""
     from .. import _lib
     flat = values.reshape(-1)
     if flat.dtype != torch.float32:
@@ -154,7 +156,9 @@ def order_statistics(values, ranks):
     lib = _lib.load()
     chunk = 32                                                          # QD_ORDER_STATS_MAX_RANKS
     if distinct.size > ORDER_STATS_MAX_PASSES * chunk or n >= 2 ** 32:
-        ordered = torch.sort(flat)[0]
+        # torch.sort's radix path on the device orders by the bit pattern: a NaN with its sign bit set (0xFFC00000, what 0/0
+        # gives on x86) comes out FIRST, before -inf, where np.partition and the select put every NaN last.  One sign for all.
+        ordered = torch.sort(torch.where(torch.isnan(flat), flat.new_full((), float('nan')), flat))[0]
         return ordered[torch.from_numpy(ranks).to(flat.device)].cpu().numpy()
     flat = flat.contiguous()
     out = torch.empty(distinct.size, dtype=torch.float32, device=flat.device)
@@ -176,12 +180,19 @@ def initialize_quantization_points(tensor, scaling_function, num_points):
     the scaling (K2) runs on the device, the 2*num_points order statistics the interpolation needs
     are SELECTED on the device (order_statistics: three reads of the tensor, no sort) and only they
     are copied back; the interpolation itself is numpy's, so the result is bit-identical
-    (tests/golden/misc.npz)."""
+    (tests/golden/misc.npz).
+
+    A NaN anywhere in the scaled tensor -- a NaN in the tensor, or a +-inf, which makes its whole bucket's alpha or beta
+    non-finite -- makes EVERY point NaN, as np.percentile does: numpy looks at the largest element after its partition
+    (NaNs order last) and returns NaN for all percentiles if that is one.  Rank n - 1 is among the fetched ranks anyway (the
+    100th percentile), so the same decision costs nothing here (tests/golden/select_percentile.json)."""
     n = tensor.numel()
     scaled = scaling_function.scale_down(tensor).view(-1)[0:scaling_function.original_tensor_length]
     lower, upper, gamma = percentile_ranks(n, num_points)
-    found = order_statistics(scaled, np.concatenate([lower, upper]))
-    values = percentile_lerp(found[:num_points], found[num_points:], gamma)
+    found = order_statistics(scaled, np.concatenate([lower, upper, [n - 1]]))     # (n - 1 is upper[-1] unless num_points == 1)
+    values = percentile_lerp(found[:num_points], found[num_points:2 * num_points], gamma)
+    if np.isnan(found[-1]):
+        values = np.full_like(values, np.nan)
     return torch.from_numpy(values).type_as(tensor).to(tensor.device)
 
 

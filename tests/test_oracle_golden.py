@@ -92,6 +92,33 @@ def test_init_points(golden_misc):
         assert np.array_equal(p, G.z['ip%d_p' % i]), (c, p, G.z['ip%d_p' % i])
 
 
+def test_init_points_of_nonfinite_tensors():
+    """tests/golden/select_percentile.json (gen_select_percentile.py: the staged reference on the percentile cases of
+    tests/select_cases.py): one NaN in the scaled tensor -- a NaN, or a +-inf through its bucket's alpha and beta -- and every
+    point is NaN; the clean tensor of each shape keeps its points bit for bit."""
+    import json
+    import os
+    import zlib
+
+    import select_cases as S
+    from conftest import GOLDEN
+    with open(os.path.join(GOLDEN, 'select_percentile.json')) as f:
+        recorded = {c['id']: c for c in json.load(f)['cases']}
+    assert len(recorded) == len(S.PCT_SHAPES) * len(S.PCT_POISONS) == 156
+    poisoned = 0
+    for shape in S.PCT_SHAPES:
+        for cid, x, bucket, k in S.percentile_cases(shape):
+            c = recorded[cid]
+            assert (c['n'], c['bucket'], c['k']) == (x.size, bucket, k) and c['input_crc32'] == zlib.crc32(x.tobytes()), cid
+            want = np.array(c['points_bits'], np.uint32).view(np.float32)
+            with np.errstate(invalid='ignore'):
+                got = onp.init_points_percentile(x, bucket, k)
+            S.same_points(got, want, cid)
+            assert bool(np.isnan(want).all()) == ('clean' not in cid) and np.isnan(want).any() == np.isnan(want).all(), cid
+            poisoned += int(np.isnan(want).all())
+    assert poisoned == 144
+
+
 def test_kats_from_survey():
     """Hand-checkable known answers (generated from the reference)."""
     x = np.array([0, 0.1, 0.25, 0.5, 0.75, 0.9, 1, -1], dtype=np.float32)
