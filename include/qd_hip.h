@@ -54,6 +54,21 @@
  *     where w is NaN (|NaN| > limit is false) and zeroes it where w is +-inf.
  *   - qd_ste_bucket_backward_f32, qd_multi_ste_backward_f32: a bucket of x that holds a NaN or an infinity quantizes to NaN
  *     as a whole; out is NaN at the first such element (tie mode REFERENCE: at the bucket's first element) and g elsewhere.
+ *   - qd_uniform_abs_f32, qd_scale_down_abs_f32, qd_inv_scale_abs_f32 ('absmax' / 'absnorm'; device only).  The reference's
+ *     lines raise, so the rules are torch's operations on their evident repair: with v = x after mean subtraction and
+ *     clamping, sign = torch.sign(v), m = |v|, norm = m.max(dim) or sqrt(sum m^2) in fp32 (oracle/oracle_np.py and, in torch's
+ *     CPU ops, oracle/torch_port.py; tests/abs_cases.py, tests/test_abs_cases_host.py, tests/test_hip_abs.py):
+ *       . a NaN anywhere in a bucket makes that bucket's norm NaN and every u, q and inverse output of it NaN; every other
+ *         bucket is bit-identical to the same call without the NaN;
+ *       . sign is 0 for a NaN of either sign bit and any payload and for +-0, and +-1 otherwise (+-inf and denormals too);
+ *       . a bucket with +-inf and no NaN has norm +inf: u is 0 for its finite elements and NaN for its infinite ones, q and
+ *         the inverse outputs are NaN as a whole (0 x inf);
+ *       . absnorm: the squares are fp32 and their sum is rounded to fp32 before the square root, so a finite bucket whose sum
+ *         of squares exceeds FLT_MAX has norm +inf (and falls under the rule above) and squares that underflow to 0
+ *         contribute nothing; an ordinary norm is within (5e-7 + 2^-22) of sqrt(sum x^2) taken in float64;
+ *       . a norm below 1e-10 is replaced by 1 after the reduction; a NaN norm stays NaN;
+ *       . the padding of a ragged last bucket (copies of the last element) obeys the same rules: a NaN last element pads u
+ *         with NaN and sign with 0.
  */
 #ifndef QD_HIP_H
 #define QD_HIP_H

@@ -328,39 +328,74 @@ def init_points_percentile(x, bucket, k, max_element=False, subtract_mean=False)
 
 # ----------------------------------------------------------------------------- absmax / absnorm
 # PARITY UNPINNED: the reference's code for these scaling types (quant_functions.py:109-127,144-146)
-# raises on every torch version, so there is nothing to pin against.  This restates the math
-# those lines evidently intend; it only checks that the HIP kernels do what DESIGN.md says.
-def scale_down_abs(x, bucket=None, kind='absmax', norm=None):
-    """sign, u = |x| / norm_b with norm_b = max|x| ('absmax') or sqrt(sum x^2) ('absnorm') per bucket,
-    norm < 1e-10 -> 1.  `norm` overrides the per-bucket norms (fp32 summation order of the L2 norm
-    is implementation specific).  Returns dict(u, sign, norm) in the padded bucket layout."""
+# raises on every torch version, so there is no reference OUTPUT to pin against.  This restates the math
+# those lines evidently intend, one fp32 operation per torch op of the repaired lines, with the rules of
+# include/qd_hip.h (NaN / inf section, abs paragraph); oracle/torch_port.py states the same with torch's
+# own CPU ops and tests/test_abs_cases_host.py holds the two together.
+def torch_sign(t):
+    """torch.sign: 0 for +-0 and for a NaN of either sign bit and any payload (np.sign gives NaN), +-1 otherwise."""
+    t = np.asarray(t, dtype=F32)
+    return np.where(t > 0, F32(1.0), np.where(t < 0, F32(-1.0), F32(0.0))).astype(F32)
+
+
+def abs_norm(m, kind):
+    """Per-row norm of the magnitudes m (2-D, fp32) before the 1e-10 guard: max (a NaN propagates, as torch.max), or
+    sqrt(sum m^2) with fp32 squares (they overflow to inf and underflow to 0 as torch's do), the sum of those squares taken
+    in float64 and rounded to fp32 once, fp32 square root."""
+    if kind == 'absmax':
+        return m.max(axis=1, keepdims=True).astype(F32)
+    with np.errstate(over='ignore', under='ignore', invalid='ignore'):
+        sq = (m * m).astype(F32)
+        return np.sqrt(sq.astype(np.float64).sum(axis=1, keepdims=True).astype(F32)).astype(F32)
+
+
+def scale_down_abs(x, bucket=None, kind='absmax', norm=None, max_element=False, subtract_mean=False, mean=None):
+    """sign, u = |v| / norm_b with v = x after mean subtraction and clamping (as scale_down) and norm_b = max|v| ('absmax')
+    or sqrt(sum v^2) ('absnorm') per bucket, norm < 1e-10 -> 1 (a NaN norm stays).  `norm` overrides the per-bucket norms
+    (the summation order of the L2 norm is implementation specific), `mean` the fp32 mean.  Returns dict(u, sign, norm, mean,
+    n, shape); u and sign in the padded bucket layout."""
     x = np.asarray(x, dtype=F32)
-    v = x.reshape(-1)
+    v = x.reshape(-1).copy()
     n = v.size
-    t = bucketize(v, bucket)
-    t2 = t.reshape(1, -1) if bucket is None else t
-    sign = np.sign(t2).astype(F32)
-    m = np.abs(t2)
-    if norm is None:
-        if kind == 'absmax':
-            nrm = m.max(axis=1, keepdims=True).astype(F32)
+    with np.errstate(invalid='ignore'):
+        if subtract_mean:
+            mu = F32(np.mean(v, dtype=np.float64)) if mean is None else F32(mean)
+            v = (v - mu).astype(F32)
         else:
-            nrm = np.sqrt((m.astype(np.float64) ** 2).sum(axis=1, keepdims=True)).astype(F32)
-        nrm = np.where(nrm < F32(TOL_DIFF_ZERO), F32(1.0), nrm).astype(F32)
-    else:
-        nrm = np.asarray(norm, dtype=F32).reshape(-1, 1)
-    u = (m / nrm).astype(F32)
-    return dict(u=u.reshape(t.shape), sign=sign.reshape(t.shape), norm=nrm.reshape(-1), n=n, shape=x.shape)
+            mu = F32(0.0)
+        if max_element is not False:
+            me = F32(max_element)
+            v = np.where(v > me, me, v)
+            v = np.where(v < -me, -me, v).astype(F32)
+        t = bucketize(v, bucket)
+        t2 = t.reshape(1, -1) if bucket is None else t
+        sign = torch_sign(t2)
+        m = np.abs(t2)
+        if norm is None:
+            nrm = abs_norm(m, kind)
+            nrm = np.where(nrm < F32(TOL_DIFF_ZERO), F32(1.0), nrm).astype(F32)
+        else:
+            nrm = np.asarray(norm, dtype=F32).reshape(-1, 1)
+        u = (m / nrm).astype(F32)
+    return dict(u=u.reshape(t.shape), sign=sign.reshape(t.shape), norm=nrm.reshape(-1), mean=mu, n=n, shape=x.shape)
 
 
-def uniform_quantize_abs(x, s, bucket=None, kind='absmax', norm=None):
-    sd = scale_down_abs(x, bucket, kind, norm)
+def inv_scale_down_abs(u, sign, norm, mean, n, shape):
+    """y = u * norm_b * sign + mean, one rounding each, padding dropped."""
+    nrm = np.asarray(norm, dtype=F32).reshape(-1, 1)
+    with np.errstate(invalid='ignore', over='ignore'):
+        y = (np.asarray(u, dtype=F32).reshape(nrm.size, -1) * nrm).astype(F32)
+        y = (y * np.asarray(sign, dtype=F32).reshape(y.shape)).astype(F32)
+        y = (y + F32(mean)).astype(F32)
+    return y.reshape(-1)[:n].reshape(shape)
+
+
+def uniform_quantize_abs(x, s, bucket=None, kind='absmax', norm=None, max_element=False, subtract_mean=False, mean=None):
+    sd = scale_down_abs(x, bucket, kind, norm, max_element, subtract_mean, mean)
     sm1 = F32(s - 1)
     u2 = sd['u'].reshape(sd['norm'].size, -1)
-    w = (np.rint((u2 * sm1).astype(F32)).astype(F32) / sm1).astype(F32)
-    y = (w * sd['norm'].reshape(-1, 1)).astype(F32)
-    y = (y * sd['sign'].reshape(u2.shape)).astype(F32)
-    y = (y + F32(0.0)).astype(F32)
+    with np.errstate(invalid='ignore', over='ignore'):
+        w = (np.rint((u2 * sm1).astype(F32)).astype(F32) / sm1).astype(F32)
     out = dict(sd)
-    out['q'] = y.reshape(-1)[:sd['n']].reshape(sd['shape'])
+    out['q'] = inv_scale_down_abs(w, sd['sign'], sd['norm'], sd['mean'], sd['n'], sd['shape'])
     return out

@@ -4,12 +4,19 @@
 // PARITY UNPINNED: the reference's implementation (quantization/quant_functions.py:109-127,
 // 144-146) raises on every torch version (`tensor.max(p=2, ...)` is not a valid call; `:126` stores
 // a bound method), so there is no reference output to compare with.  These kernels implement the
-// math those lines evidently intend, and are checked against oracle/oracle_np.py's restatement
-// of the same intent only:
+// math those lines evidently intend, and are checked against two independent CPU statements of it,
+// oracle/oracle_np.py and (torch's own ops) oracle/torch_port.py, on the cases of tests/abs_cases.py:
 //     sign = sign(x); m = |x|; norm_b = max_b(m) or sqrt(sum_b m^2); norm < 1e-10 -> 1
 //     u = m / norm_b                                   (scale_down)
 //     x' = u * norm_b * sign (+ mean)                  (inv_scale_down)
 //     q = rint(u*(s-1))/(s-1) * norm_b * sign (+mean)  (uniformQuantization)
+// NaN / inf (include/qd_hip.h has the rules; they are what torch's sign, abs, max(dim), sum, sqrt and / give): the max
+// is NaN-propagating (pmax), so a NaN makes its bucket's norm and with it every u, q and inverse output of the bucket
+// NaN and touches no other bucket; sign is 0 for NaN and +-0, +-1 otherwise; an infinity gives norm +inf, u 0 or NaN,
+// q NaN.  absnorm squares in fp32 (overflow -> +inf, underflow -> 0), adds the squares in double and rounds the sum to
+// fp32 once before sqrtf: within (5e-7 + 2^-22) of the float64 norm on any order of magnitudes.  The 1e-10 guard
+// runs after the reduction and leaves a NaN norm alone.  The padding of a ragged last bucket follows the same rules.
+// No atomics: two calls give the same bits.
 // Not a hot path (no driver reaches it): one wave per bucket, two passes, the second from L1/L2;
 // a whole-tensor bucket uses a two-stage reduction.
 #include "qd_common.h"
@@ -24,18 +31,27 @@ constexpr int kParts = 1024;
 
 __device__ __forceinline__ float signf(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
-// reduce |x| over [lo, hi) with a wave: max or sum of squares
+// norm < 1e-10 -> 1 after the reduction; the comparison is false for a NaN norm, which stays
+__device__ __forceinline__ float guard_norm(float nrm) { return nrm < QD_TOL_DIFF_ZERO ? 1.0f : nrm; }
+
+// reduce |x| over [lo, hi) with a wave: max (pmax: a NaN propagates) or sum of squares.  The squares are fp32 (they
+// overflow and underflow as torch's do); each lane adds its squares in double -- an fp32 running sum drops a small square
+// next to a large sum entirely, 3e-5 of the sum on 4096, 0.7, 0.7, ... -- and the sum is rounded to fp32 once, before the
+// root.  `extra_sq`: the squares of the padding of a ragged last bucket.
 template <int NORM>
 __device__ __forceinline__ float wave_norm(const float* x, int64_t lo, int64_t hi, int lane, const Prep& pp,
-                                           float extra_sq) {
-    float acc = 0.0f;
+                                           double extra_sq) {
+    if (NORM == 0) {
+        float acc = 0.0f;
+        for (int64_t i = lo + lane; i < hi; i += 64) acc = pmax(acc, fabsf(prep(x[i], pp)));
+        return guard_norm(wave_max(acc));
+    }
+    double acc = 0.0;
     for (int64_t i = lo + lane; i < hi; i += 64) {
         const float m = fabsf(prep(x[i], pp));
-        acc = NORM == 0 ? fmaxf(acc, m) : acc + m * m;
+        acc += (double)(m * m);
     }
-    acc = NORM == 0 ? wave_max(acc) : wave_sum(acc) + extra_sq;
-    float nrm = NORM == 0 ? acc : sqrtf(acc);
-    return nrm < QD_TOL_DIFF_ZERO ? 1.0f : nrm;
+    return guard_norm(sqrtf((float)(wave_sum_d(acc) + extra_sq)));
 }
 
 // OP 0: quantize-dequantize; 1: scale_down (writes u and sign, padded layout); 
@@ -54,10 +70,10 @@ __global__ __launch_bounds__(256) void k_abs_buckets(const float* x, float* out,
         const int64_t hi = lo + row < n ? lo + row : n;
         // the reference pads the ragged last bucket with copies of the last element BEFORE taking the
         // norm (help_functions.py:76-86): copies cannot change a max, but they do enter an L2 norm
-        float extra_sq = 0.0f;
+        double extra_sq = 0.0;
         if (NORM == 1 && pad && hi < lo + row && hi == n && nb > 1) {
             const float ml = fabsf(prep(x[n - 1], pp));
-            extra_sq = (float)(lo + row - hi) * (ml * ml);
+            extra_sq = (double)(lo + row - hi) * (double)(ml * ml);
         }
         const float nrm = norm_in ? norm_in[norm_stride ? bkt : 0] : wave_norm<NORM>(x, lo, hi, lane, pp, extra_sq);
         if (lane == 0 && norm_out && !norm_in) norm_out[bkt] = nrm;
@@ -89,34 +105,44 @@ __global__ __launch_bounds__(256) void k_abs_buckets(const float* x, float* out,
 
 template <int NORM>
 __global__ __launch_bounds__(256) void k_abs_partial(const float* x, int64_t n, const float* mean, float me, float* part) {
-    __shared__ float red[4];
+    __shared__ double red[4];
     Prep pp;
     pp.mean = mean ? *mean : 0.0f;
     pp.me = me;
-    float acc = 0.0f;
+    // max: pmax, a NaN propagates.  Sum of squares: fp32 squares added in double per thread (see wave_norm); the block's
+    // partial is rounded to fp32 once (2^-24 of the sum at most over all partials), the scratch stays kParts floats.
+    float mx = 0.0f;
+    double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float m = fabsf(prep(x[i], pp));
-        acc = NORM == 0 ? fmaxf(acc, m) : acc + m * m;
+        if (NORM == 0) mx = pmax(mx, m);
+        else acc += (double)(m * m);
     }
-    acc = NORM == 0 ? wave_max(acc) : wave_sum(acc);
+    if (NORM == 0) acc = (double)wave_max(mx);            // (exact: a float, NaN included, survives the round trip)
+    else acc = wave_sum_d(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0)
-        part[blockIdx.x] = NORM == 0 ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
+        part[blockIdx.x] = NORM == 0 ? pmax(pmax((float)red[0], (float)red[1]), pmax((float)red[2], (float)red[3]))
+                                     : (float)((red[0] + red[1]) + (red[2] + red[3]));
 }
 template <int NORM>
 __global__ __launch_bounds__(256) void k_abs_final(const float* part, int nparts, float* norm_out) {
     __shared__ double red[4];
+    float mx = 0.0f;
     double acc = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) acc = NORM == 0 ? fmax(acc, (double)part[i]) : acc + (double)part[i];
-    if (NORM == 0) { for (int s = 1; s < 64; s <<= 1) acc = fmax(acc, __shfl_xor(acc, s)); }
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        if (NORM == 0) mx = pmax(mx, part[i]);
+        else acc += (double)part[i];
+    }
+    if (NORM == 0) acc = (double)wave_max(mx);
     else acc = wave_sum_d(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double t = NORM == 0 ? fmax(fmax(red[0], red[1]), fmax(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
-        float nrm = NORM == 0 ? (float)t : sqrtf((float)t);
-        norm_out[0] = nrm < QD_TOL_DIFF_ZERO ? 1.0f : nrm;
+        const float nrm = NORM == 0 ? pmax(pmax((float)red[0], (float)red[1]), pmax((float)red[2], (float)red[3]))
+                                    : sqrtf((float)((red[0] + red[1]) + (red[2] + red[3])));
+        norm_out[0] = guard_norm(nrm);
     }
 }
 

@@ -766,8 +766,9 @@ def abs_case(op, tag, x, bucket, kind, px, pq, ps, mean=None, me=None):
     """op 0: qd_uniform_abs_f32, 1: qd_scale_down_abs_f32, 2: qd_inv_scale_abs_f32 (on the oracle's u, sign and norm)."""
     n = x.size
     nb, npad = nbuckets(n, bucket), padded(n, bucket)
-    v, name = _prep(x, mean, me), ('absmax', 'absnorm')[kind]
-    ref = onp.scale_down_abs(v, bucket or None, name)
+    name = ('absmax', 'absnorm')[kind]
+    opts = dict(max_element=False if me is None else me, subtract_mean=mean is not None, mean=mean)
+    ref = onp.scale_down_abs(x, bucket or None, name, **opts)
     norm_want = ref['norm'].reshape(-1) if kind == 0 else Near(ref['norm'].reshape(-1), 2e-6)
     mean_arr = [('mean', inp(np.array([mean], np.float32), 4))] if mean is not None else []
     m = Ref('mean') if mean is not None else None
@@ -788,16 +789,12 @@ def abs_case(op, tag, x, bucket, kind, px, pq, ps, mean=None, me=None):
 
     def expect():
         if op == 2:
-            row = bucket if nb > 1 else n
-            y = (ref['u'].reshape(nb, -1) * ref['norm'].reshape(nb, 1)).astype(np.float32) * ref['sign'].reshape(nb, -1)
-            y = (y.astype(np.float32) + np.float32(mean or 0.0)).astype(np.float32)
-            return {'y': y.reshape(-1)[:n]}
+            return {'y': onp.inv_scale_down_abs(ref['u'], ref['sign'], ref['norm'], ref['mean'], n, (n,))}
         if op == 1:
-            return {'norm': norm_want, 'u': AfterNorm(lambda nrm: onp.scale_down_abs(v, bucket or None, name, norm=nrm)['u'].reshape(-1)),
+            return {'norm': norm_want, 'u': AfterNorm(lambda nrm: onp.scale_down_abs(x, bucket or None, name, norm=nrm, **opts)['u'].reshape(-1)),
                     'sign': ref['sign'].reshape(-1)}
         return {'norm': norm_want,
-                'q': AfterNorm(lambda nrm: (onp.uniform_quantize_abs(v, 8, bucket or None, name, norm=nrm)['q'].reshape(-1)
-                                            + np.float32(mean or 0.0)).astype(np.float32))}
+                'q': AfterNorm(lambda nrm: onp.uniform_quantize_abs(x, 8, bucket or None, name, norm=nrm, **opts)['q'].reshape(-1))}
     return case(tag, ent, arrays, args, expect)           # (the header states no minimum for the two-stage norm's scratch)
 
 

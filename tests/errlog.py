@@ -84,3 +84,16 @@ def check_ste(kind, out, x, g, s, bucket, tag='', tol=TOL, tie_mode='reference',
     assert np.all(err[~nz] == 0), (kind, tag)
     assert ratio <= tol, (kind, tag, 'bucket-sum error / (sum|terms| + |g_j|) = %.3g > %.1g' % (ratio, tol))
     return ratio
+
+
+def check_norm(kind, got, want, tag='', tol=TOL, n_terms=None):
+    """An L2 norm: got = the kernel's fp32 norms, want = sqrt(sum x^2) in float64 from exact squares (all > 0).  Requires
+    |got - want| <= tol * want -- the terms are squares, so a relative error e of their sum is e / 2 of the norm: callers pass
+    tests/abs_cases.py: BOUND -- and records max |got - want| / want."""
+    got = np.asarray(got, dtype=np.float64).reshape(-1)
+    want = np.asarray(want, dtype=np.float64).reshape(-1)
+    assert got.shape == want.shape and np.all(want > 0), (kind, tag, got.shape, want.shape)
+    ratio = float(np.max(np.abs(got - want) / want)) if got.size else 0.0
+    _record(kind, tag, ratio, n_terms, tol)
+    assert ratio <= tol, (kind, tag, '|norm - norm64| / norm64 = %.3g > %.3g' % (ratio, tol))
+    return ratio
