@@ -101,7 +101,7 @@ extern "C" {
  * changed meaning).  qd_multi_dq_plan / qd_multi_nearest_f32 / qd_multi_point_grad_f32 take bucket == 0, buckets that are
  * no power of two and k up to 256, also without a bump: arguments that were rejected are now accepted; nothing existing
  * changed meaning.  qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 / qd_multi_ste_backward_levels_f32 (a level
- * count per tensor) are new symbols, likewise without a bump; so is qd_transform_plan (host only).
+ * count per tensor) are new symbols, likewise without a bump; so are qd_transform_plan and qd_set_grid_cap (host only).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -122,6 +122,19 @@ size_t qd_workspace_bytes(void);
  * Returns the previous mode; any other value restores the default.  The only switch of this path (no environment
  * variable).  Process-wide, not thread-safe against concurrent launches. */
 int qd_set_single_fused_mode(int mode);
+
+/* Test hook: the cap on the number of blocks of every launch whose grid is sized from the problem.  The kernels loop over
+ * tiles, chunks or buckets with a grid stride, but the default cap of 1 << 20 blocks only bounds the grid dimension, so the
+ * second and later trips of those loops run only above billions of elements (and, in the nearest-point mode with the fine
+ * cell table, above 24 blocks per compute unit).  Under a cap of 1, 2 or 3 blocks a tensor of a few thousand elements makes
+ * them (tests/test_hip_grid_trips.py).  Every launch site takes min(its own cap, this cap) blocks; qd_transform_plan plans
+ * under the cap that is set.  Not capped: grids that are not a free function of the problem size -- the one-launch single
+ * bucket kernel (co-resident by construction), single-block folds, one block per output row, the fixed 2048-wave grid of
+ * qd_multi_point_grad_f32, one block per Huffman chunk (csrc/qd_common.h lists them).
+ *   blocks in 1 .. 1 << 20 sets the cap; any other value restores the default, 1 << 20.  Returns the previous value.
+ * Results never depend on the cap, only the launch geometry does.  Process-wide, not thread-safe against concurrent
+ * launches; no environment variable. */
+int qd_set_grid_cap(int blocks);
 
 /* Number of buckets / padded length of the bucket view (help_functions.py:67-94). Host only. */
 int64_t qd_num_buckets(int64_t n, int64_t bucket);

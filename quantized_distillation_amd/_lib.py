@@ -94,6 +94,7 @@ SIGNATURES = {
     'qd_error_string': (ctypes.c_char_p, [c_int]),
     'qd_workspace_bytes': (c_size, []),
     'qd_set_single_fused_mode': (c_int, [c_int]),
+    'qd_set_grid_cap': (c_int, [c_int]),                   # test hook: blocks per problem-sized launch; returns the previous cap
     'qd_num_buckets': (i64, [i64, i64]),
     'qd_padded_length': (i64, [i64, i64]),
     'qd_transform_plan': (c_int, [c_p, i64, c_p]),         # tables of QdTransformQuery / QdTransformPlan (ctypes or numpy memory)

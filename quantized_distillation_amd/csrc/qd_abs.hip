@@ -157,8 +157,7 @@ __global__ __launch_bounds__(256) void k_abs_inverse(const float* u, const float
 }
 
 inline int nblocks(int64_t items, int per) {
-    int64_t b = (items + per - 1) / per;
-    return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+    return grid_blocks(items, per, 65536);                     // (qd_common.h: the site's own cap and the grid-cap hook)
 }
 
 template <int OP>

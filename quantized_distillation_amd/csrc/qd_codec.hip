@@ -672,9 +672,7 @@ __global__ __launch_bounds__(256) void k_zero_u64(unsigned long long* p, int n) 
 }
 
 inline int blocks_for(int64_t items, int per_block, int cap) {
-    int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    return (int)(b < cap ? b : cap);
+    return grid_blocks(items, per_block, cap);                 // (qd_common.h: the site's own cap and the grid-cap hook)
 }
 
 }  // namespace
@@ -698,7 +696,7 @@ int qd_pack_uniform_f32(const float* x, int64_t n, int64_t bucket, int levels, i
 #define QD_PACK(LPB, V)                                                                                              \
     {                                                                                                                \
         const int64_t tiles = (nfull + (64 / LPB) - 1) / (64 / LPB);                                                 \
-        const int blocks = blocks_for(tiles, 4, 1 << 20);                                                            \
+        const int blocks = blocks_for(tiles, 4, kNoOwnCap);                                                            \
         if (bits == 8) hipLaunchKernelGGL((k_pack_vec<LPB, V, 8>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
         else if (bits == 4) hipLaunchKernelGGL((k_pack_vec<LPB, V, 4>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
         else if (bits == 2) hipLaunchKernelGGL((k_pack_vec<LPB, V, 2>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
@@ -730,7 +728,7 @@ int qd_pack_levels_u8(const uint8_t* levels_idx, int64_t n, int bits, uint8_t* p
         return QD_ERR_INVALID_ARGUMENT;
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int blocks = blocks_for(n / (32 / bits) + 1, 256 * 4, 1 << 20);
+    const int blocks = blocks_for(n / (32 / bits) + 1, 256 * 4, kNoOwnCap);
     if (bits == 8) hipLaunchKernelGGL(k_pack_levels<8>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
     else if (bits == 4) hipLaunchKernelGGL(k_pack_levels<4>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
     else if (bits == 2) hipLaunchKernelGGL(k_pack_levels<2>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
@@ -751,7 +749,7 @@ int qd_unpack_uniform_f32(const uint8_t* packed, int64_t n, int64_t bucket, int 
         hipStream_t st2 = (hipStream_t)stream;
         const float sm1b = (float)(levels - 1);
         const int64_t bk = (bucket == 0 || n < bucket) ? 0 : bucket;
-        const int blocks2 = blocks_for((n + 3) / 4, 256 * 4, 1 << 20);
+        const int blocks2 = blocks_for((n + 3) / 4, 256 * 4, kNoOwnCap);
         if (bits == 8) hipLaunchKernelGGL(k_unpack_any<8>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
         else if (bits == 4) hipLaunchKernelGGL(k_unpack_any<4>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
         else if (bits == 2) hipLaunchKernelGGL(k_unpack_any<2>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
@@ -762,7 +760,7 @@ int qd_unpack_uniform_f32(const uint8_t* packed, int64_t n, int64_t bucket, int 
     while (((int64_t)1 << row_shift) < bucket) ++row_shift;
     hipStream_t st = (hipStream_t)stream;
     const float sm1 = (float)(levels - 1);
-    const int blocks = blocks_for((n + 3) / 4, 256 * 4, 1 << 20);
+    const int blocks = blocks_for((n + 3) / 4, 256 * 4, kNoOwnCap);
     if (bits == 8) hipLaunchKernelGGL(k_unpack<8>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
     else if (bits == 4) hipLaunchKernelGGL(k_unpack<4>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
     else if (bits == 2) hipLaunchKernelGGL(k_unpack<2>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);

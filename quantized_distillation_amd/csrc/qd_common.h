@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qd_plan.h"         // capped_blocks(), kDefaultGridCap
+
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef int64_t l2 __attribute__((ext_vector_type(2)));
 
@@ -60,6 +62,35 @@ inline int device_cus() {
         if (cached) __atomic_store_n(&cache[dev], v, __ATOMIC_RELAXED);
     }
     return v;
+}
+
+// ---- the grid cap, and the ONE function every problem-sized grid goes through ----
+// qd_set_grid_cap() (include/qd_hip.h; a test hook, process-wide, a plain int: set it before launching, not concurrently)
+// lowers the number of blocks of every launch whose grid is sized from the problem, so that the second and later trips of
+// the kernels' grid-stride loops run at shapes of a few thousand elements.  The variable is defined in qd_kernels.hip and
+// hidden: not part of the ABI.  Its default is the cap of the grid dimension (qd_plan.h: kDefaultGridCap), which no shipped
+// shape reaches below 2^31 elements, so the default changes no launch.
+extern "C" __attribute__((visibility("hidden"))) int qd_grid_cap_state;
+inline int hook_grid_cap() { return qd_grid_cap_state; }
+// ceil(items / per_block) blocks, at least 1, at most min(own_cap, the hook's cap).  own_cap: what the launch site itself
+// allows (compute units x blocks per CU, rows of a partial buffer, ...); kNoOwnCap where it has none (qd_plan.h).
+// NOT sized through here, each because its grid is not a free function of the problem size:
+//   k_single_fused                       the grid must be co-resident and hold the tensor in registers: fused_blocks (qd_plan.h)
+//   k_minmax_final, k_mean_final, k_arg_final, k_abs_final, k_zero_u64, k_pack_tail, k_sel_pick_top, k_huf_scan
+//                                        one block
+//   k_point_grad_final, k_multi_point_grad_final, k_hist_fold, k_mg_fold, k_sel_sum_top, k_sel_pick_sub
+//                                        one block per OUTPUT row (point, histogram bin, tensor, rank): blockIdx IS the row
+//                                        (K10, qd_select.hip: its two radix passes k_sel_hist_top / k_sel_hist_sub stride by
+//                                        gridDim and ARE sized here -- the same `blocks` tells the pick kernels how many
+//                                        partial rows to sum; only its pick / sum launches are of this kind)
+//   k_multi_point_grad (K6m)             a fixed grid: 2048 waves that stride over the full tiles + one wave per tensor; the
+//                                        partial rows qd_multi_dq_plan laid out are indexed by that wave number
+//   k_huf_chunk_words, k_huf_write, k_huf_decode
+//                                        one block (lane) per chunk of the coded stream: the chunk table is indexed by it, and
+//                                        the caller fixes the chunk count
+//   k_selftest_div                       the self-test's own grid, not a product launch
+inline int grid_blocks(int64_t items, int64_t per_block, int64_t own_cap) {
+    return capped_blocks(items, per_block, own_cap, hook_grid_cap());
 }
 
 // ---- NaN-propagating min / max ----

@@ -22,6 +22,7 @@
 
 
 extern "C" int qd_fused_mode_state = 1;       // see qd_transform.h
+extern "C" int qd_grid_cap_state = kDefaultGridCap;   // see qd_common.h
 
 
 // ================================ C ABI ========================================================
@@ -32,6 +33,11 @@ int qd_abi_version(void) { return QD_ABI_VERSION; }
 int qd_set_single_fused_mode(int mode) {
     const int prev = qd_fused_mode_state;
     qd_fused_mode_state = (mode >= 0 && mode <= 4) ? mode : 1;
+    return prev;
+}
+int qd_set_grid_cap(int blocks) {
+    const int prev = qd_grid_cap_state;
+    qd_grid_cap_state = (blocks >= 1 && blocks <= kDefaultGridCap) ? blocks : kDefaultGridCap;
     return prev;
 }
 const char* qd_target_arch(void) { return "gfx950"; }
@@ -75,7 +81,7 @@ int qd_transform_plan(const QdTransformQuery* queries, int64_t count, QdTransfor
         in.data_misalign = q.data_misalign; in.side_bytes = q.side_bytes; in.side_misalign = q.side_misalign;
         in.k = q.k; in.assign_mode = q.assign_mode; in.prescaled = q.prescaled != 0; in.q_null = q.q_null != 0;
         in.fused_ok = q.fused_capacity > 0;
-        in.cus = q.cus; in.grid_cap = kDefaultGridCap;
+        in.cus = q.cus; in.grid_cap = grid_cap();
         const TransformPlan pl = plan_transform(in);
         QdTransformPlan& o = plans[i];
         o = QdTransformPlan{};

@@ -443,8 +443,7 @@ int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t tot
         return QD_ERR_INVALID_ARGUMENT;
     if (total_tiles == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    int64_t b = (total_tiles + 3) / 4;
-    const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
+    const int blocks = grid_blocks(total_tiles, 4, kNoOwnCap);
     if (bucket == 0) hipLaunchKernelGGL(k_multi_nearest_flat, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, points, k);
     else if (bucket == 256) hipLaunchKernelGGL((k_multi_nearest<256>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);
     else if (bucket == 128) hipLaunchKernelGGL((k_multi_nearest<128>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k);

@@ -604,8 +604,7 @@ int qd_multi_uniform_global_f32(const QdTensorDesc* table, int ntensors, int64_t
         return QD_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    int64_t b = (total_tiles + 3) / 4;
-    const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
+    const int blocks = blocks_for(total_tiles, 4);
     hipLaunchKernelGGL(k_mg_minmax, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, part);
     hipLaunchKernelGGL(k_mg_fold, dim3(ntensors), dim3(256), 0, st, table, ntensors, total_tiles, part, alpha_beta);
     hipLaunchKernelGGL(k_mg_apply, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, alpha_beta,
@@ -625,8 +624,7 @@ int qd_multi_uniform_global_opt_f32(const QdTensorDesc* table, int ntensors, int
         return QD_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    int64_t b = (total_tiles + 3) / 4;
-    const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
+    const int blocks = blocks_for(total_tiles, 4);
     const float sm1 = (float)(levels - 1);
     hipLaunchKernelGGL(k_mg_minmax_opt, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, part, me);
     hipLaunchKernelGGL(k_mg_fold, dim3(ntensors), dim3(256), 0, st, table, ntensors, total_tiles, part, alpha_beta);
@@ -680,8 +678,7 @@ int qd_multi_uniform_global_levels_f32(const QdTensorDesc* table, const int32_t*
         return QD_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     float* part = (float*)workspace;
-    int64_t b = (total_tiles + 3) / 4;
-    const int blocks = (int)(b < (1 << 20) ? b : (1 << 20));
+    const int blocks = blocks_for(total_tiles, 4);
     hipLaunchKernelGGL(k_mg_minmax_opt, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, part, me);
     hipLaunchKernelGGL(k_mg_fold, dim3(ntensors), dim3(256), 0, st, table, ntensors, total_tiles, part, alpha_beta);
     if (stochastic)

@@ -138,7 +138,7 @@ struct PlanInput {
     bool q_null;             // MODE_NEAREST: indices only
     bool fused_ok;           // the one-launch single-bucket kernel may be tried: not switched off, not in place
     int cus;                 // compute units of the device
-    int grid_cap;            // kDefaultGridCap (QD_TUNING builds: QD_GRID_CAP)
+    int grid_cap;            // kDefaultGridCap, or what qd_set_grid_cap() set (QD_TUNING builds: QD_GRID_CAP)
 };
 
 struct TransformPlan {
@@ -161,10 +161,16 @@ struct TransformPlan {
     bool ab_ready;           // k_single_apply finds (alpha, beta) in the scratch slot (copied, or folded by k_minmax_final); else it folds nparts partials
 };
 
-inline int blocks_for(int64_t items, int per_block, int cap) {
+// The grid of a launch that is sized from the problem: ceil(items / per_block) blocks, at least 1, at most the launch
+// site's own cap (kNoOwnCap: none) and the grid cap -- kDefaultGridCap, or what qd_set_grid_cap() set.  Every such launch
+// goes through this one function: the plan below with its input's grid_cap, the launchers through grid_blocks()
+// (qd_common.h), which passes the hook's value.
+constexpr int64_t kNoOwnCap = (int64_t)1 << 30;
+inline int capped_blocks(int64_t items, int64_t per_block, int64_t own_cap, int64_t grid_cap) {
     int64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    return (int)(b < cap ? b : cap);
+    const int64_t cap = own_cap < grid_cap ? own_cap : grid_cap;
+    if (b > cap) b = cap;
+    return (int)(b < 1 ? 1 : b);
 }
 
 // lanes of a chunk kernel that reduce side by side: above 64 buckets a lane reduces whole buckets alone, below that 64 / m
@@ -192,13 +198,15 @@ inline TransformPlan plan_transform(const PlanInput& in) {
     auto one = [&pl](int family, int a, int b, int c, int blocks, int threads, size_t lds) {
         pl.launch[pl.nlaunch++] = Launch{family, a, b, c, blocks, threads, lds};
     };
-    auto capped = [fine_cap](int blocks) { return blocks < fine_cap ? blocks : fine_cap; };
+    // grid(items, per_block, own_cap): capped_blocks() under the input's grid cap; `fine_cap` is the own cap of the kernels
+    // that build the fine table
+    auto grid = [&in](int64_t items, int64_t per_block, int64_t own_cap) { return capped_blocks(items, per_block, own_cap, in.grid_cap); };
 
     // K5 at any bucket size from 4 elements: the pre-processed forward as a plain stream (qd_nearest.hip).  One bucket with a
     // q output: the single-bucket apply kernel already is a plain stream.
     if (nearest && in.prescaled && n >= 4 && row >= 4 && !(nb <= 1 && !in.q_null) && data_ok &&
         (!side || (in.side_misalign & (in.side_bytes == 8 ? 15 : 3)) == 0)) {
-        one(FAM_PRESCALED_STREAM, (row & 3) != 0, 0, 0, capped(blocks_for(n >> 2, 256 * kStreamU, in.grid_cap)), 256, tb);
+        one(FAM_PRESCALED_STREAM, (row & 3) != 0, 0, 0, grid(n >> 2, 256 * kStreamU, fine_cap), 256, tb);
         return pl;                                      // one 4 KiB tile per wave
     }
     if (in.q_null) return pl;                           // (n < 4, a bucket below 4 elements, or a misaligned base): nothing serves it
@@ -220,12 +228,12 @@ inline TransformPlan plan_transform(const PlanInput& in) {
         if (prescaled) {
             pl.copies_ab = pl.ab_ready = true;
         } else {
-            pl.nparts = blocks_for(n, 256 * 4 * 8, in.grid_cap < kPartialBlocks ? in.grid_cap : kPartialBlocks);
+            pl.nparts = grid(n, 256 * 4 * 8, kPartialBlocks);
             one(FAM_MINMAX_PARTIAL, 0, 0, 0, pl.nparts, 256, 0);
             pl.ab_ready = n > kFoldLaunchN;
             if (pl.ab_ready) one(FAM_MINMAX_FINAL, 0, 0, 0, 1, 256, 0);
         }
-        one(FAM_SINGLE_APPLY, 0, 0, 0, capped(blocks_for(n, 256 * 4 * 4, in.grid_cap)), 256, tb);
+        one(FAM_SINGLE_APPLY, 0, 0, 0, grid(n, 256 * 4 * 4, fine_cap), 256, tb);
         return pl;
     }
 
@@ -239,8 +247,8 @@ inline TransformPlan plan_transform(const PlanInput& in) {
             /* the vector kernel hides the narrowed search behind 7 waves per SIMD up to 64 points (99 us against 104 us with */ \
             /* the fine table on a capped grid); the kernels with fewer resident waves gain from 33 points on */     \
             if (in.k <= 64) pl.fine = 0;                                                                              \
-            const int blocks = blocks_for((nfull + bpw - 1) / bpw, 4, in.grid_cap) + 1;   /* +1: the block that owns the tail */ \
-            one(FAM_VEC, LPB, V, U, pl.fine ? capped(blocks) : blocks, 256, nearest ? point_table_bytes(in.k, pl.fine) : 0); \
+            const int blocks = grid((nfull + bpw - 1) / bpw, 4, kNoOwnCap) + 1;           /* +1: the block that owns the tail */ \
+            one(FAM_VEC, LPB, V, U, pl.fine && blocks > fine_cap ? fine_cap : blocks, 256, nearest ? point_table_bytes(in.k, pl.fine) : 0); \
         }
         QD_VEC_SHAPES(QD_PLAN_VEC)
 #undef QD_PLAN_VEC
@@ -268,7 +276,7 @@ inline TransformPlan plan_transform(const PlanInput& in) {
             if (V > 16)
                 while (pl.nbk > 0 && ((((pl.nbk * row < n ? pl.nbk * row : n) + 3) >> 2) << 2) > n) --pl.nbk;
             pl.amask = ~(int64_t)31;
-            one(FAM_WAVE_ANY, V, G, 0, capped(blocks_for(pl.nbk > 0 ? pl.nbk : 1, 4 / G, in.grid_cap)), 256, tb);
+            one(FAM_WAVE_ANY, V, G, 0, grid(pl.nbk > 0 ? pl.nbk : 1, 4 / G, fine_cap), 256, tb);
             return pl;
         }
     }
@@ -283,7 +291,7 @@ inline TransformPlan plan_transform(const PlanInput& in) {
             pl.nchunks = nfull / m;
             pl.fine = 0;                                // the chunk kernels stage data in LDS: coarse table
             // two waves per block: pairs, (alpha, beta), 1/alpha
-            one(FAM_CHUNK, kChunkV, 0, 0, blocks_for(pl.nchunks, 2, in.grid_cap) + 1 /* the block that owns the tail */, 128,
+            one(FAM_CHUNK, kChunkV, 0, 0, grid(pl.nchunks, 2, kNoOwnCap) + 1 /* the block that owns the tail */, 128,
                 (size_t)2 * (kChunkV * 64 + 256 + 128) * 8 + tbc);
             return pl;
         }
@@ -306,16 +314,16 @@ inline TransformPlan plan_transform(const PlanInput& in) {
             pl.nchunks = nfull / m;
             pl.fine = 0;
             // two waves: the staged chunk, + a byte per element when level / point indices (<= 255) are asked for
-            one(FAM_CHUNK_ANY, kChunkV, 0, 0, blocks_for(pl.nchunks, 2, in.grid_cap) + 1, 128,
+            one(FAM_CHUNK_ANY, kChunkV, 0, 0, grid(pl.nchunks, 2, kNoOwnCap) + 1, 128,
                 (size_t)2 * (kChunkV * 256 + (stage8(mode, side, side, in.k) ? kChunkV * 64 : 0)) * 4 + tbc);
             return pl;
         }
     }
     // misaligned, or too few full buckets for one chunk, or (nearest point) a bucket above 9216 elements: two passes, the
     // second from L1 / L2
-    if (row <= 256) one(FAM_GROUPS, 16, 0, 0, capped(blocks_for(nb, 16, in.grid_cap)), 256, tb);          // 16 buckets per block, a DPP row each
-    else if (row <= 16384) one(FAM_GROUPS, 64, 0, 0, capped(blocks_for(nb, 4, in.grid_cap)), 256, tb);    // 4 buckets per block, one wave each
-    else one(FAM_GENERIC, 0, 0, 0, capped(blocks_for(nb, 1, in.grid_cap)), 1024, tb);
+    if (row <= 256) one(FAM_GROUPS, 16, 0, 0, grid(nb, 16, fine_cap), 256, tb);          // 16 buckets per block, a DPP row each
+    else if (row <= 16384) one(FAM_GROUPS, 64, 0, 0, grid(nb, 4, fine_cap), 256, tb);    // 4 buckets per block, one wave each
+    else one(FAM_GENERIC, 0, 0, 0, grid(nb, 1, fine_cap), 1024, tb);
     return pl;
 }
 

@@ -334,9 +334,8 @@ int qd_order_stats_f32(const float* x, int64_t n, const int64_t* ranks, int m, f
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
     const int cus = device_cus();
     constexpr int U = 4;
-    int64_t want = (n + (int64_t)SEL_THREADS * 4 * U - 1) / ((int64_t)SEL_THREADS * 4 * U);
     const int cap = cus < MAX_BLOCKS ? cus : MAX_BLOCKS;
-    const int blocks = (int)(want < 1 ? 1 : (want > cap ? cap : want));
+    const int blocks = grid_blocks(n, (int64_t)SEL_THREADS * 4 * U, cap);      // both radix passes, and the rows of `part` the pick kernels read
     const size_t lds = (size_t)m * SUB_BINS * sizeof(uint32_t);
     // the attribute is per DEVICE: raise it once for each device this process launches on
     static std::atomic<unsigned long long> lds_raised{0};

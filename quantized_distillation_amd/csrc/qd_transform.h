@@ -1693,9 +1693,9 @@ inline int grid_cap() {
     const int v = e ? atoi(e) : 0;
     if (v > 0) return v;
 #endif
-    return kDefaultGridCap;
+    return hook_grid_cap();                                    // kDefaultGridCap unless qd_set_grid_cap() lowered it (qd_common.h)
 }
-inline int blocks_for(int64_t items, int per_block) { return qd::blocks_for(items, per_block, grid_cap()); }
+inline int blocks_for(int64_t items, int per_block) { return capped_blocks(items, per_block, kNoOwnCap, grid_cap()); }
 
 inline int check_launch() {
     const hipError_t e = hipGetLastError();

@@ -58,7 +58,7 @@ def test_every_compute_entry_point_checks_its_arguments_before_touching_the_devi
     workspace -- every compute entry point returns QD_ERR_INVALID_ARGUMENT without a launch (this runs on a box without a
     GPU), the way the reference's functions raise ValueError before any work (quant_functions.py:22-33,230-236)."""
     import ctypes
-    host_only = {'qd_abi_version', 'qd_target_arch', 'qd_error_string', 'qd_workspace_bytes', 'qd_set_single_fused_mode', 'qd_num_buckets',
+    host_only = {'qd_abi_version', 'qd_target_arch', 'qd_error_string', 'qd_workspace_bytes', 'qd_set_single_fused_mode', 'qd_set_grid_cap', 'qd_num_buckets',
                  'qd_padded_length', 'qd_transform_plan', 'qd_multi_plan', 'qd_multi_global_plan', 'qd_multi_dq_plan', 'qd_packed_bytes',
                  'qd_order_stats_workspace_bytes'}
     checked = 0
@@ -254,7 +254,8 @@ def test_write_once_outputs_keep_their_non_temporal_hint(lib):
 def test_no_environment_knobs_in_the_product(lib):
     """One code path per configuration: the product library reads no environment variable (round 2 shipped nine QD_*
     A/B knobs that switched between alternative kernel implementations at run time).  libqd_hip.so neither imports
-    getenv nor contains a QD_* name; the only run-time switch is the documented qd_set_single_fused_mode()."""
+    getenv nor contains a QD_* name; the only run-time switches are the two documented setters, qd_set_single_fused_mode()
+    and the test hook qd_set_grid_cap()."""
     blob = open(_lib.LIB_PATH, 'rb').read()
     names = set(re.findall(rb'QD_[A-Z][A-Z0-9_]{2,}', blob))
     assert not names, names

@@ -236,8 +236,10 @@ def test_uniform_random_sweep_vs_c_oracle(bucket):
 
 @pytest.mark.parametrize('bucket', [33, 50, 7, 250, 511, 100, 1000, 513])
 def test_uniform_chunk_kernels_many_chunks_per_wave(bucket):
-    """16.7 M elements: more chunks than a resident grid of the chunk kernels holds, so a wave that works through several
-    chunks (persistent / prefetching launch shapes) is exercised; stochastic branch too (the draw is indexed by element)."""
+    """16.7 M elements: many chunks per LAUNCH -- thousands of blocks of the chunk kernels, more than are resident at once --
+    stochastic branch too (the draw is indexed by element).  Not several chunks per wave: the grid has a wave per chunk (bucket
+    33: about 4 237 blocks for 8 473 chunks), so each wave's loop runs once here; the later trips of that loop are
+    tests/test_hip_grid_trips.py's, under qd_set_grid_cap."""
     n = (1 << 24) + 12345
     x = (torch.randn(n, generator=torch.Generator().manual_seed(bucket)) * 0.3).numpy()
     q, sf = quantization.uniformQuantization(dev(x), 16, bucket_size=bucket)

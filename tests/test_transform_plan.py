@@ -183,10 +183,11 @@ def check_contracts(q, p, seen):
                 raise AssertionError('a kernel this test has no contract for: ' + name)
 
 
-def the_sweep(lib):
+def the_sweep(lib, check_contracts=check_contracts):
     """Every bucket size 1 .. 40000 x four lengths, in every mode, with the variations of the module docstring; returns the set
     of kernel names planned.  (Unaligned pointers send every size to the two-pass kernels, and the side outputs change LDS
-    sizes only: those variations run once per mode, not crossed with each other.)"""
+    sizes only: those variations run once per mode, not crossed with each other.)  `check_contracts`: what holds every batch
+    (the capped sweep below adds its own assertions to the contracts)."""
     seen = set()
     n, b = sweep_lengths(np.arange(1, MAX_BUCKET + 1))
     configs = [dict(mode=QDQ), dict(mode=QDQ, side_bytes=1), dict(mode=QDQ, data_misalign=2), dict(mode=QDQ, side_bytes=1, side_misalign=1),
@@ -231,6 +232,65 @@ def test_capacity_contracts_hold_for_every_bucket_size_and_every_shipped_instant
     # (exceptions would be listed here by name, each with its reason; there are none)
     assert stranded == [], 'shipped instantiations that no swept input reaches: %s' % stranded
     assert len(seen) == 82                       # the transform kernels of profiles/r06_launch_coverage.json
+
+
+TAIL_OWNER = re.compile(r'^k_bucket_(vec|chunk|chunk_any)<')      # these plan one block more: the block that owns the tail
+GRID_CAP_DEFAULT = 1 << 20
+
+
+@pytest.mark.parametrize('cap', [1, 2, 3, 7])
+def test_the_plan_under_a_small_grid_cap_changes_the_geometry_and_never_the_kernel(lib, cap):
+    """qd_set_grid_cap (the test hook that makes the kernels' grid-stride loops take their later trips at small shapes,
+    tests/test_hip_grid_trips.py): the sweep again under a cap of 1, 2, 3 and 7 blocks.  The capacity contracts still hold,
+    every launch has at most `cap` blocks (+ 1 in the families with a tail-owner block; k_single_fused is exempt: its grid must
+    hold the tensor in registers) and at most `cap` min / max partials, and the kernels and everything they index with -- m,
+    nchunks, nbk, nvec, fine -- are those of the uncapped plan."""
+    def check(q, p, seen):
+        check_contracts(q, p, seen)
+        assert lib.qd_set_grid_cap(-1) == cap                  # the uncapped plan of the same batch
+        try:
+            p0 = plan(lib, q)
+        finally:
+            assert lib.qd_set_grid_cap(cap) == GRID_CAP_DEFAULT
+        for f in ('nb', 'row', 'nvec', 'm', 'nchunks', 'nbk', 'amask', 'fine', 'nlaunch'):
+            assert np.array_equal(p[f], p0[f]), f
+        for j in range(3):
+            live = p['nlaunch'] > j
+            L, L0 = p['launch'][live, j], p0['launch'][live, j]
+            assert np.array_equal(L['kernel'], L0['kernel']) and np.array_equal(L['threads'], L0['threads'])
+            assert np.array_equal(L['lds_bytes'], L0['lds_bytes'])
+            for name in np.unique(L['kernel']):
+                s = L['kernel'] == name
+                name = name.decode()
+                if name.startswith('k_single_fused<'):
+                    assert np.array_equal(L['blocks'][s], L0['blocks'][s]), name
+                    continue
+                room = cap + 1 if TAIL_OWNER.match(name) else cap
+                assert np.all(L['blocks'][s] == np.minimum(L0['blocks'][s], room)), name      # hence <= room, and nparts <= cap
+                if name == 'k_minmax_partial':
+                    assert np.all(L['blocks'][s] <= cap), name                              # its blocks ARE the partials (nparts)
+
+    assert lib.qd_set_grid_cap(cap) == GRID_CAP_DEFAULT
+    try:
+        seen = the_sweep(lib, check)
+    finally:
+        assert lib.qd_set_grid_cap(-1) == cap
+    assert lib.qd_set_grid_cap(GRID_CAP_DEFAULT) == GRID_CAP_DEFAULT       # reads back as the default
+    assert len(seen) == 82
+
+
+def test_the_grid_cap_hook_takes_1_to_2_pow_20_and_restores_the_default_otherwise(lib):
+    try:
+        assert lib.qd_set_grid_cap(5) == GRID_CAP_DEFAULT and lib.qd_set_grid_cap(GRID_CAP_DEFAULT) == 5
+        for bad in (0, -1, GRID_CAP_DEFAULT + 1, 1 << 30):
+            assert lib.qd_set_grid_cap(3) == GRID_CAP_DEFAULT and lib.qd_set_grid_cap(bad) == 3
+        assert lib.qd_set_grid_cap(1) == GRID_CAP_DEFAULT
+        p = plan(lib, queries(QDQ, 1 << 26, 256))[0]                      # the headline call under a cap of one block (+ the tail owner)
+        assert (p['nvec'], p['launch'][0]['blocks']) == (1 << 18, 2)
+    finally:
+        lib.qd_set_grid_cap(-1)
+    p = plan(lib, queries(QDQ, 1 << 26, 256))[0]
+    assert p['launch'][0]['blocks'] == (1 << 14) + 1
 
 
 W = 'k_bucket_wave_any<%d,'
