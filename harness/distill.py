@@ -21,7 +21,7 @@ import numbers
 import torch
 
 import quantization
-from quantized_distillation_amd import ste
+from quantized_distillation_amd import _lib, ste
 from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer, MultiTensorSTE
 
 from . import models
@@ -62,6 +62,11 @@ class DistillTrainer(object):
             num_bits = list(num_bits)
             if any(isinstance(b, bool) or not isinstance(b, numbers.Real) or int(b) != b or b < 1 for b in num_bits):
                 raise ValueError('num_bits must be a positive integer, or a sequence of them with one entry per parameter')
+        for b in (num_bits if per_param else [num_bits]):      # 2**bits levels: inside the range of the level count, or refused now
+            try:
+                _lib.level_count(2 ** b)
+            except (ValueError, OverflowError, TypeError):
+                raise ValueError('num_bits = %r: 2**num_bits levels leave the accepted range [2, 2^31 - 1]' % (b,))
         self.device = device
         # optional: the teacher forward (needs neither the quantized weights nor the student) on its own HIP
         # stream beside quantize + student forward, joined before the KD loss.  Measured on the CIFAR step:

@@ -198,7 +198,13 @@ int qd_mean_f32(const float* x, int64_t n, float* mean_out, void* workspace, siz
  * as the reference computes it.  level_idx is saturated at levels - 1 there (it keeps its documented range; at
  * levels == 256 the value 256 has no byte to go to).  The seed is a by-value launch argument: a captured launch replays
  * the same draws (the Python layer refuses a stochastic call during stream capture for that reason).
- * workspace is only used when the tensor is a single bucket (bucket == 0 or n < bucket). */
+ * workspace is only used when the tensor is a single bucket (bucket == 0 or n < bucket).
+ * levels: 2 .. 2^31 - 1 (INT_MAX), here and in every entry point that takes a level count; below 2 is
+ * QD_ERR_INVALID_ARGUMENT.  A deliberate narrowing of the reference, whose quantizers take any s (they never convert it):
+ * `levels` is an int, so a larger count cannot cross this ABI, and every Python entry point raises ValueError for one
+ * instead of passing a truncated value on (2^32 + 16 would arrive as 16).  levels - 1 is converted to fp32 once, rounded to
+ * nearest even as the reference's tensor ops round the Python int: exact up to 2^24 + 1 levels, 2^31 at 2^31 - 1 levels.
+ * Nothing converts a level back to an integer except level_idx (levels <= 256). */
 int qd_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int levels, float* alpha, float* beta,
                    uint8_t* level_idx, const float* mean, int clamp, float max_element, int stochastic,
                    uint64_t seed, void* workspace, size_t workspace_bytes, void* stream);

@@ -41,6 +41,9 @@ def lib():
         L.qdo_uniform_f32.restype = None
         L.qdo_uniform_f32.argtypes = [_f, _f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _f, _f, _i64, _i64, _i32,
                                       ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float]
+        L.qdo_uniform_stochastic_f32.restype = None
+        L.qdo_uniform_stochastic_f32.argtypes = [_f, _f, _f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _f, _f,
+                                                 ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float]
         L.qdo_scale_down_f32.restype = None
         L.qdo_scale_down_f32.argtypes = [_f, _f, ctypes.c_int64, ctypes.c_int64, _f, _f, _i64, _i64,
                                          ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float]
@@ -77,8 +80,20 @@ def num_buckets(n, bucket):
     return int(lib().qdo_num_buckets(n, bucket or 0))
 
 
+S_MAX = 2 ** 31 - 1
+
+
+def _levels(s):
+    """s as the C `int` of qd_oracle.c -- or ValueError: ctypes would mask a larger value (2^32 + 16 would quantize with 16
+    levels), and an oracle must never agree with a truncation.  oracle_np takes any s, as the reference does."""
+    if isinstance(s, bool) or int(s) != s or not 2 <= s <= S_MAX:
+        raise ValueError('oracle_c: s must be an integer in [2, 2^31 - 1], got %r (use oracle_np beyond it)' % (s,))
+    return int(s)
+
+
 def uniform_quantize(x, s, bucket=None, max_element=False, subtract_mean=False, mean=None,
                      want_idx=True, want_lev=True):
+    s = _levels(s)
     x = _c(x)
     flat = x.reshape(-1)
     n = flat.size
@@ -95,6 +110,25 @@ def uniform_quantize(x, s, bucket=None, max_element=False, subtract_mean=False, 
                           int(max_element is not False), float(max_element or 0.0))
     return dict(q=q.reshape(x.shape), alpha=alpha, beta=beta, imin=imin, imax=imax, lev=lev,
                 mean=np.float32(mean or 0.0))
+
+
+def uniform_quantize_stochastic(x, s, rand, bucket=None, max_element=False, subtract_mean=False, mean=None):
+    """The stochastic branch given the draw of every element (rand: n values, unpadded; oracle_np takes the padded layout)."""
+    s = _levels(s)
+    x = _c(x)
+    flat = x.reshape(-1)
+    n = flat.size
+    rand = _c(rand).reshape(-1)
+    assert rand.size == n
+    nb = num_buckets(n, bucket)
+    q = np.empty(n, np.float32)
+    alpha, beta = np.empty(nb, np.float32), np.empty(nb, np.float32)
+    if subtract_mean and mean is None:
+        mean = lib().qdo_mean_f32(_p(flat, _f), n)
+    lib().qdo_uniform_stochastic_f32(_p(flat, _f), _p(rand, _f), _p(q, _f), n, bucket or 0, s, _p(alpha, _f), _p(beta, _f),
+                                     int(bool(subtract_mean)), float(mean or 0.0), int(max_element is not False),
+                                     float(max_element or 0.0))
+    return dict(q=q.reshape(x.shape), alpha=alpha, beta=beta, mean=np.float32(mean or 0.0))
 
 
 def scale_down(x, bucket=None, max_element=False, subtract_mean=False, mean=None):
@@ -137,6 +171,7 @@ def point_grad(g, idx, alpha, bucket, k):
 
 
 def ste_complicated_backward(x, g, s, bucket):
+    s = _levels(s)
     x, g = _c(x), _c(g)
     out = np.empty(x.size, np.float32)
     lib().qdo_ste_backward_f32(_p(x.reshape(-1), _f), _p(g.reshape(-1), _f), _p(out, _f), x.size, bucket or 0, s)

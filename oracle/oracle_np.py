@@ -107,7 +107,8 @@ def uniform_quantize(x, s, bucket=None, max_element=False, subtract_mean=False, 
     w = (r / sm1).astype(F32)                                     # :191
     q = inv_scale_down(w, sd['alpha'], sd['beta'], sd['mean'], sd['n'], sd['shape'])   # :193
     out = dict(sd)
-    out.update(q=q, lev=np.where(np.isnan(r), F32(0.0), r).astype(np.int32))   # NaN: level 0, what both libraries store
+    # NaN: level 0, what both libraries store; s = 2^31 - 1: s - 1 rounds to 2^31 in fp32, past int32 -- saturated
+    out.update(q=q, lev=np.minimum(np.where(np.isnan(r), F32(0.0), r).astype(np.float64), 2147483647.0).astype(np.int32))
     return out
 
 
@@ -129,7 +130,7 @@ def uniform_quantize_stochastic(x, s, rand, bucket=None, max_element=False, subt
     q = inv_scale_down(w, sd['alpha'], sd['beta'], sd['mean'], sd['n'], sd['shape'])
     lev = np.minimum(fl + up.astype(F32), sm1)                    # (NaN stays NaN through np.minimum)
     out = dict(sd)
-    out.update(q=q, lev=np.where(np.isnan(lev), F32(0.0), lev).astype(np.int32), up=up)
+    out.update(q=q, lev=np.minimum(np.where(np.isnan(lev), F32(0.0), lev).astype(np.float64), 2147483647.0).astype(np.int32), up=up)
     return out
 
 

@@ -142,7 +142,7 @@ void qdo_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int s,
             float y = w * a;  y = y + b;            /* :142-143 */
             if (sub_mean) y = y + mean;             /* :148 (mean 0 is an exact no-op) */
             q[i] = y;
-            if (lev) lev[i] = r != r ? 0 : (int32_t)r;   /* NaN: level 0, what both libraries store (include/qd_hip.h) */
+            if (lev) lev[i] = r != r ? 0 : r >= 2147483648.0f ? INT32_MAX : (int32_t)r;   /* NaN: level 0 (include/qd_hip.h); 2^31 saturates */
         }
         return;
     }
@@ -162,7 +162,40 @@ void qdo_uniform_f32(const float* x, float* q, int64_t n, int64_t bucket, int s,
             float y = w * a;  y = y + b;
             if (sub_mean) y = y + mean;
             q[i] = y;
-            if (lev) lev[i] = r != r ? 0 : (int32_t)r;   /* NaN: level 0, what both libraries store (include/qd_hip.h) */
+            if (lev) lev[i] = r != r ? 0 : r >= 2147483648.0f ? INT32_MAX : (int32_t)r;   /* NaN: level 0 (include/qd_hip.h); 2^31 saturates */
+        }
+    }
+}
+
+/* uniformQuantization, stochastic rounding, given the uniform [0, 1) draw of every element (rnd[n], unpadded).
+ * quant_functions.py:174-187, one rounded fp32 operation per tensor op: probabilities = s * u, floor, probabilities -= floor,
+ * floor / s, + (rnd <= probabilities) * 1 / s. */
+void qdo_uniform_stochastic_f32(const float* x, const float* rnd, float* q, int64_t n, int64_t bucket, int s, float* alpha,
+                                float* beta, int sub_mean, float mean, int clamp, float me) {
+    int64_t nb, row;
+    geometry(n, bucket, &nb, &row);
+    const float sm1 = (float)(s - 1); /* :172 */
+#pragma omp parallel for schedule(static)
+    for (int64_t b_ = 0; b_ < nb; ++b_) {
+        int64_t lo = b_ * row, hi = lo + row < n ? lo + row : n;
+        float a, b;
+        bucket_stats(x, lo, hi, sub_mean, mean, clamp, me, &a, &b, 0, 0);
+        if (alpha) alpha[b_] = a;
+        if (beta) beta[b_] = b;
+        for (int64_t i = lo; i < hi; ++i) {
+            float v = prep(x[i], sub_mean, mean, clamp, me);
+            float u = v - b;  u = u / a;
+            float p = sm1 * u;                      /* :179 */
+            float t = u * sm1;                      /* :180 */
+            float l = floorf(t);                    /* :181 */
+            p = p - l;                              /* :182 */
+            float w = l / sm1;                      /* :183 */
+            float inc = (rnd[i] <= p ? 1.0f : 0.0f) * 1.0f;
+            inc = inc / sm1;                        /* :187 */
+            w = w + inc;
+            float y = w * a;  y = y + b;
+            if (sub_mean) y = y + mean;
+            q[i] = y;
         }
     }
 }

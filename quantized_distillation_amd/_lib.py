@@ -253,10 +253,31 @@ def mark_written(tensors):
     glue().mark_written(tensors)
 
 
-def check(code):
+def check(code, lib=None):
+    """Raise for a non-zero return code of the C ABI, described by the library that returned it: `lib` is that library
+    (lib_for(tensor) / host() / load()); None means libqd_hip.so.  A CPU call that is refused must not need the HIP library to
+    say why."""
     if code != 0:
-        msg = load().qd_error_string(code)
-        raise RuntimeError('qd_hip: %s (code %d)' % (msg.decode() if msg else '?', code))
+        if lib is None:
+            lib = load()
+        msg = lib.qd_error_string(code)
+        raise RuntimeError('%s: %s (code %d)' % ('qd_host' if lib is _host else 'qd_hip', msg.decode() if msg else '?', code))
+
+
+LEVELS_MIN, LEVELS_MAX = 2, 2 ** 31 - 1      # `levels` is an int in the C ABI (include/qd_hip.h, next to qd_uniform_f32)
+
+
+def level_count(s, what='s'):
+    """The level count `s` of every uniform entry point as an int, or ValueError: an integral number (16.0 is 16) in
+    [2, 2^31 - 1].  The reference takes any s (its quantizers never convert it); here it crosses the C ABI as an `int`, and
+    a larger value would arrive truncated -- 2^32 + 16 as 16 -- so it is refused before anything is launched."""
+    try:                                       # (int() of an infinity raises OverflowError, of a NaN ValueError, of None TypeError)
+        ok = not isinstance(s, (bool, str, bytes)) and bool(int(s) == s) and LEVELS_MIN <= int(s) <= LEVELS_MAX
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError('%s must be an integer >= 2 in the accepted range [2, 2^31 - 1] (2147483647), got %r' % (what, s))
+    return int(s)
 
 
 # ---------------------------------------------------------------- torch plumbing (memory, stream)

@@ -55,8 +55,7 @@ def pack_uniform(tensor, s, bucket_size=256, bits=None):
     _lib.require_device_f32(tensor)
     if bucket_size is not None and (not isinstance(bucket_size, int) or isinstance(bucket_size, bool) or bucket_size <= 0):
         raise ValueError('Bucket size must be an integer and strictly positive. Pass None if you want to avoid using buckets')
-    if int(s) != s or s < 2:
-        raise ValueError('s must be an integer >= 2')
+    s = _lib.level_count(s)
     bits = bits_for_levels(s) if bits is None else bits
     if bits not in (1, 2, 4, 8) or s > (1 << bits):
         raise ValueError('bits must be 1, 2, 4 or 8 and hold s levels')
@@ -105,6 +104,9 @@ def level_histogram(tensor, s, bucket_size=None):
     per element, nothing written but s counters).  Other bucket geometries (bucket_size None, any other size, a misaligned
     view) write the uint8 levels with the quantize kernel and count those."""
     _lib.require_device_f32(tensor)
+    s = _lib.level_count(s)
+    if s > 256:
+        raise ValueError('the level histogram holds at most 256 levels')
     x = tensor.contiguous().view(-1)
     if _lib.on_other_device(x):
         with torch.cuda.device(x.device):
@@ -132,6 +134,7 @@ def huffman_mean_bit_length_uniform(params, s, bucket_size=None):
     get_huffman_encoding_mean_bit_length(..., 'uniform', s) computes it
     (ref: help_functions.py:175-232), with the histogram built on the device: only s counters per
     model cross PCIe instead of every quantized tensor."""
+    s = _lib.level_count(s)
     total = None
     for p in params:
         t = p.data if hasattr(p, 'data') else p

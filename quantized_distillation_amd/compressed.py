@@ -169,7 +169,7 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
             raise ValueError('s must be an integer in 2 .. 256, or a sequence of them with one entry per quantized tensor')
         s_list = None if scalar else list(s)
         for v in ([s] if scalar else s_list):
-            if isinstance(v, bool) or not isinstance(v, numbers.Real) or int(v) != v or not 2 <= v <= 256:
+            if _lib.level_count(v, 's (2 .. 256 in a compressed file)') > 256:        # the shared range check first
                 raise ValueError('s must be an integer in 2 .. 256, or a sequence of them with one entry per quantized tensor')
     params = _named(tensors, 'tensors')
     bufs = _named(buffers, 'buffers')
@@ -225,17 +225,17 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
             bk = bucket_size or 0
             if mode == 0:               # K1 with its uint8 level output: the symbols and the alpha / beta of uniformQuantization
                 _lib.check(lib.qd_uniform_f32(x.data_ptr(), scratch.data_ptr(), n, bk, levels[j], a_p, b_p,
-                                              sym.data_ptr() + sym_off[j], None, 0, 0.0, 0, 0, wsp, wsn, st))
+                                              sym.data_ptr() + sym_off[j], None, 0, 0.0, 0, 0, wsp, wsn, st), lib)
             else:                       # K4 with uint8 point indices: those of nonUniformQuantization
                 p = pts[j].to(dev)
                 _lib.check(lib.qd_nearest_point_f32(x.data_ptr(), 0, p.data_ptr(), levels[j], 0, scratch.data_ptr(),
-                                                    sym.data_ptr() + sym_off[j], 1, n, bk, a_p, b_p, None, 0, 0.0, wsp, wsn, st))
+                                                    sym.data_ptr() + sym_off[j], 1, n, bk, a_p, b_p, None, 0, 0.0, wsp, wsn, st), lib)
         fb += nbs[j]
     # histogram of every stored symbol (the zero padding between tensors is taken off symbol 0)
     pad = sym.numel() - nsym
     if cuda:
         hist = torch.empty(256, dtype=torch.int64, device=dev)
-        _lib.check(lib.qd_histogram_u8_ws(sym.data_ptr(), sym.numel(), 256, hist.data_ptr(), wsp, wsn, st))
+        _lib.check(lib.qd_histogram_u8_ws(sym.data_ptr(), sym.numel(), 256, hist.data_ptr(), wsp, wsn, st), lib)
         counts = hist.cpu().numpy().astype(np.int64)
     else:
         counts = np.bincount(sym.numpy(), minlength=256).astype(np.int64)
@@ -274,10 +274,10 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
             table_d = _lib.upload_struct(table, dev)
             code_d = _lib.upload_struct(code, dev)
             _lib.check(lib.qd_huffman_encode(table_d.data_ptr(), len(quant), nchunks, code_d.data_ptr(), chunk_words.data_ptr(),
-                                             words.data_ptr(), max_words, st))
+                                             words.data_ptr(), max_words, st), lib)
         else:
             _lib.check(lib.qd_huffman_encode(ctypes.addressof(table), len(quant), nchunks, ctypes.addressof(code),
-                                             chunk_words.data_ptr(), words.data_ptr(), max_words, None))
+                                             chunk_words.data_ptr(), words.data_ptr(), max_words, None), lib)
         chunk_np = chunk_words.cpu().numpy().view(np.uint32)
         nwords = int(chunk_np[-1])
         if nwords > max_words:
@@ -536,8 +536,8 @@ def _decode(f, data, res, device):
         code_d = _lib.upload_struct(code, device)
         _lib.check(lib.qd_huffman_decode_f32(ptr(words), f.nwords, chunk_words.data_ptr(), table_d.data_ptr(), len(q), f.nchunks,
                                              code_d.data_ptr(), alpha.data_ptr(), beta.data_ptr(), ptr(pts),
-                                             _lib.stream_ptr(device)))
+                                             _lib.stream_ptr(device)), lib)
         _lib.mark_written([res[e['name']] for e in q])
     else:
         _lib.check(lib.qd_huffman_decode_f32(ptr(words), f.nwords, chunk_words.data_ptr(), ctypes.addressof(table), len(q),
-                                             f.nchunks, ctypes.addressof(code), alpha.data_ptr(), beta.data_ptr(), ptr(pts), None))
+                                             f.nchunks, ctypes.addressof(code), alpha.data_ptr(), beta.data_ptr(), ptr(pts), None), lib)

@@ -117,6 +117,10 @@ PyObject* glue_uniform(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     const int subtract_mean = PyObject_IsTrue(args[7]);
     const int in_place = PyObject_IsTrue(args[8]);
     if (PyErr_Occurred()) return nullptr;
+    if (levels < 2 || levels > 0x7fffffffL) {              // `levels` is an int in the C ABI: never truncate (2^32 + 16 is not 16)
+        PyErr_SetString(PyExc_ValueError, "s must be an integer >= 2 in the accepted range [2, 2^31 - 1]");
+        return nullptr;
+    }
 
     at::Tensor x = x0;
     if (!x.is_contiguous()) {

@@ -21,12 +21,10 @@ from . import _lib
 
 
 def _level_counts(s, tensors):
-    """s of the uniform one-launch classes: an integer >= 2 for every tensor, or a sequence of them, one per tensor.  Returns
+    """s of the uniform one-launch classes: an integer in [2, 2^31 - 1] for every tensor, or a sequence of them, one per tensor.  Returns
     (what `self.s` keeps: the int or a tuple, the list of tensors); only the list's length is looked at, no tensor is."""
     def one(v):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or int(v) != v or v < 2:
-            raise ValueError('s must be an integer >= 2, or a sequence of them with one entry per tensor')
-        return int(v)
+        return _lib.level_count(v)         # 's must be an integer >= 2 in the accepted range [2, 2^31 - 1]'
     if isinstance(s, numbers.Real) and not isinstance(s, bool):
         return one(s), tensors
     if isinstance(s, (str, bytes)) or not hasattr(s, '__iter__'):

@@ -294,6 +294,9 @@ def get_huffman_encoding_mean_bit_length(model_param_iter, quantization_function
         raise ValueError('type_quantization not recognized')
     if s is None and type_quantization == 'uniform':
         raise ValueError('If type of quantization is uniform, you must provide s')
+    if type_quantization == 'uniform':
+        from .. import _lib
+        s = _lib.level_count(s)                 # the range of every level count, before s edges are built
     if not isinstance(quantization_functions, list):
         quantization_functions = [quantization_functions]
     shared = len(quantization_functions) == 1

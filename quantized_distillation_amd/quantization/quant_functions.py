@@ -223,9 +223,9 @@ class ScalingFunction(object):
         if self.subtract_mean:
             self._mean_buf = torch.empty(1, dtype=torch.float32, device=tensor.device)
             if n > 0:
-                ws = _lib.workspace_for(tensor)
-                _lib.check(_lib.lib_for(tensor).qd_mean_f32(tensor.data_ptr(), n, self._mean_buf.data_ptr(),
-                                                            ws.data_ptr(), ws.numel(), _lib.stream_for(tensor)))
+                ws, lib = _lib.workspace_for(tensor), _lib.lib_for(tensor)
+                _lib.check(lib.qd_mean_f32(tensor.data_ptr(), n, self._mean_buf.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _lib.stream_for(tensor)), lib)
             self.mean_tensor = self._mean_buf.view(())                               # 0-dim, ref: :67
         else:
             self._mean_buf = None
@@ -265,10 +265,10 @@ class ScalingFunction(object):
         out = torch.empty(2, nb, dtype=torch.int64, device=t.device)
         clamp, me = self._clamp_args()
         if n > 0:
-            ws = _lib.workspace_for(t)
-            _lib.check(_lib.lib_for(t).qd_bucket_argminmax_f32(
+            ws, lib = _lib.workspace_for(t), _lib.lib_for(t)
+            _lib.check(lib.qd_bucket_argminmax_f32(
                 t.data_ptr(), n, _bucket_arg(self.bucket_size), _ptr(self._mean_buf), clamp, me,
-                out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_for(t)))
+                out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_for(t)), lib)
         shape = (1,) if self.bucket_size is None else (nb, 1)
         self._idx_min_rows = out[0].view(*shape)
         self._idx_max_rows = out[1].view(*shape)
@@ -315,10 +315,10 @@ class ScalingFunction(object):
         ab = self._alloc_alpha_beta(nb, tensor.device)
         clamp, me = self._clamp_args()
         if n > 0:
-            ws = _lib.workspace_for(tensor)
-            _lib.check(_lib.lib_for(tensor).qd_scale_down_f32(
+            ws, lib = _lib.workspace_for(tensor), _lib.lib_for(tensor)
+            _lib.check(lib.qd_scale_down_f32(
                 tensor.data_ptr(), out.data_ptr(), n, _bucket_arg(self.bucket_size), ab[0].data_ptr(),
-                ab[1].data_ptr(), _ptr(self._mean_buf), clamp, me, ws.data_ptr(), ws.numel(), _lib.stream_for(tensor)))
+                ab[1].data_ptr(), _ptr(self._mean_buf), clamp, me, ws.data_ptr(), ws.numel(), _lib.stream_for(tensor)), lib)
             if in_place:
                 _lib.mark_written(tensor)          # the kernel wrote over the input through its raw pointer
         return out.view(self.expected_tensor_size)
@@ -364,9 +364,10 @@ class ScalingFunction(object):
         out = tensor.view(-1)[0:n] if self.modify_in_place else torch.empty(n, dtype=torch.float32,
                                                                           device=tensor.device)
         if n > 0:
-            _lib.check(_lib.lib_for(tensor).qd_inv_scale_f32(
+            lib = _lib.lib_for(tensor)
+            _lib.check(lib.qd_inv_scale_f32(
                 tensor.data_ptr(), out.data_ptr(), n, _bucket_arg(self.bucket_size), self.alpha.data_ptr(),
-                self.beta.data_ptr(), _ptr(self._mean_buf), _lib.stream_for(tensor)))
+                self.beta.data_ptr(), _ptr(self._mean_buf), _lib.stream_for(tensor)), lib)
             if self.modify_in_place:
                 _lib.mark_written(tensor)
         return out.view(self.original_tensor_size)
@@ -382,8 +383,7 @@ def _uniform_host(tensor, s, type_of_scaling, stochastic_rounding, max_element, 
     """uniformQuantization of a CPU tensor: the same single call into the C ABI (qd_uniform_f32: per-bucket min/max, alpha/beta,
     scale, round, rescale in one pass), served by libqd_host.so.  ref: :155-194."""
     sf = ScalingFunction(type_of_scaling, max_element, subtract_mean, bucket_size, True)    # validates as the reference, :22-33,166-167
-    if int(s) != s or s < 2:
-        raise ValueError('s must be an integer >= 2')
+    s = _lib.level_count(s)
     if sf.type_scaling != 'linear':
         _abs_needs_device(tensor)
     sf.modify_in_place = modify_in_place                   # governs _begin's contiguity rule
@@ -395,9 +395,9 @@ def _uniform_host(tensor, s, type_of_scaling, stochastic_rounding, max_element, 
     clamp, me = sf._clamp_args()
     if n > 0:
         _lib.check(_lib.host().qd_uniform_f32(
-            x.data_ptr(), q.data_ptr(), n, _bucket_arg(bucket_size), int(s), ab[0].data_ptr(), ab[1].data_ptr(), None,
+            x.data_ptr(), q.data_ptr(), n, _bucket_arg(bucket_size), s, ab[0].data_ptr(), ab[1].data_ptr(), None,
             _ptr(sf._mean_buf), clamp, me, 1 if stochastic_rounding else 0,
-            next_stochastic_seed(host=True) if stochastic_rounding else 0, None, 0, None))
+            next_stochastic_seed(host=True) if stochastic_rounding else 0, None, 0, None), _lib.host())
         if modify_in_place:
             _lib.mark_written(x)
     return q.view(sf.original_tensor_size), sf
@@ -441,7 +441,7 @@ def uniformQuantization(tensor, s, type_of_scaling='linear', stochastic_rounding
             return done
     if (type_of_scaling == 'linear' and max_element is False and not modify_in_place
             and (bucket_size is None or (type(bucket_size) is int and bucket_size > 0))
-            and type(s) is int and s >= 2):
+            and type(s) is int and 2 <= s <= _lib.LEVELS_MAX):
         q, ab, mean, n, x_read = _glue_uniform(tensor, s, bucket_size or 0, False, 0.0, stochastic_rounding,
                                                next_stochastic_seed() if stochastic_rounding else 0, subtract_mean, False)
         sf = _new_object(ScalingFunction)
@@ -462,8 +462,7 @@ def uniformQuantization(tensor, s, type_of_scaling='linear', stochastic_rounding
             d['mean_tensor'] = 0                                                     # ref: :70
         return q, sf
     sf = ScalingFunction(type_of_scaling, max_element, subtract_mean, bucket_size, True)    # as the reference, :166-167
-    if int(s) != s or s < 2:
-        raise ValueError('s must be an integer >= 2')
+    s = _lib.level_count(s)
     if sf.type_scaling != 'linear':
         return _uniform_abs(tensor, s, sf, stochastic_rounding, modify_in_place)
     if modify_in_place:
@@ -479,7 +478,7 @@ def uniformQuantization(tensor, s, type_of_scaling='linear', stochastic_rounding
         with torch.cuda.device(tensor.device):
             sf._note_arg_source(tensor, overwritten=True)
     clamp = max_element is not False
-    q, ab, mean, n, x_read = _glue_uniform(tensor, int(s), bucket_size or 0, clamp, float(max_element) if clamp else 0.0,
+    q, ab, mean, n, x_read = _glue_uniform(tensor, s, bucket_size or 0, clamp, float(max_element) if clamp else 0.0,
                                            stochastic_rounding, next_stochastic_seed() if stochastic_rounding else 0,
                                            subtract_mean, modify_in_place)
     sf.original_tensor_size = q.shape
@@ -549,10 +548,11 @@ class SearchSorted:
             # the few-element / offset-view case writes its values into a throw-away buffer instead
             only = n >= 4 and self.scaled_tensor.data_ptr() % 16 == 0
             scratch = None if only else torch.empty(n, dtype=torch.float32, device=self.scaled_tensor.device)
-            _lib.check(_lib.lib_for(self.scaled_tensor).qd_nearest_point_f32(
+            lib = _lib.lib_for(self.scaled_tensor)
+            _lib.check(lib.qd_nearest_point_f32(
                 self.scaled_tensor.data_ptr(), 1, pts.data_ptr(), pts.numel(), 1, None if only else scratch.data_ptr(),
                 idx.data_ptr(), 8, n, 0, one.data_ptr(), zero.data_ptr(), None, 0, 0.0,
-                ws.data_ptr(), ws.numel(), _lib.stream_for(self.scaled_tensor)))
+                ws.data_ptr(), ws.numel(), _lib.stream_for(self.scaled_tensor)), lib)
         return idx
 
 
@@ -577,7 +577,8 @@ def _nearest(x, prescaled, points, assign_mode, n, bucket_size, alpha, beta, mea
         if n > 0:
             _lib.check(_lib.host().qd_nearest_point_f32(
                 x.data_ptr(), 1 if prescaled else 0, points.data_ptr(), points.numel(), assign_mode, q.data_ptr(), idx.data_ptr(),
-                idx_bytes, n, bucket_size or 0, alpha.data_ptr(), beta.data_ptr(), _ptr(mean_buf), clamp, me, None, 0, None))
+                idx_bytes, n, bucket_size or 0, alpha.data_ptr(), beta.data_ptr(), _ptr(mean_buf), clamp, me, None, 0, None),
+                _lib.host())
             if in_place:
                 _lib.mark_written(x)
         return q, idx
@@ -653,7 +654,7 @@ class uniformQuantization_variable(object):
 
     def __init__(self, s, type_of_scaling='linear', stochastic_rounding=False, max_element=False,
                  subtract_mean=False, modify_in_place=False, bucket_size=None):
-        self.s = s
+        self.s = _lib.level_count(s)                     # refused here, before forward() clones anything
         self.typeOfScaling = type_of_scaling
         self.stochasticRounding = stochastic_rounding
         self.maxElementAllowed = max_element
@@ -694,9 +695,10 @@ class uniformQuantization_variable(object):
         out = torch.empty_like(g)
         if x.numel() > 0:
             x = x.contiguous()
-            _lib.check(_lib.lib_for(x).qd_ste_bucket_backward_f32(
-                x.data_ptr(), g.data_ptr(), out.data_ptr(), x.numel(), int(self.bucket_size), int(self.s),
-                0 if tie_mode == 'reference' else 1, _lib.stream_for(x)))
+            lib = _lib.lib_for(x)
+            _lib.check(lib.qd_ste_bucket_backward_f32(
+                x.data_ptr(), g.data_ptr(), out.data_ptr(), x.numel(), int(self.bucket_size), _lib.level_count(self.s),
+                0 if tie_mode == 'reference' else 1, _lib.stream_for(x)), lib)
         self.saved_for_backward = None                                               # ref: :404-405
         return out.view(x.size())
 
@@ -797,7 +799,7 @@ class nonUniformQuantization_variable(object):
             grad_points = torch.empty(int(k), dtype=torch.float32)
             _lib.check(_lib.host().qd_point_grad_f32(
                 g.data_ptr(), idx.data_ptr(), 8 if idx.dtype == torch.int64 else 1, alpha.data_ptr(), g.numel(),
-                self.bucket_size or 0, int(k), grad_points.data_ptr(), None, 0, None))
+                self.bucket_size or 0, int(k), grad_points.data_ptr(), None, 0, None), _lib.host())
             self.savedIndices = None                                                  # ref: :505
             return grad_output, grad_points
         grad_points = _lib.glue().point_grad(grad_output, idx, alpha, self.bucket_size or 0, int(k))

@@ -40,7 +40,8 @@ def clamp_(weights, limit=1.0):
     w = _flat(weights, 'weights')
     if w.numel():
         with _on(w):
-            _lib.check(_lib.lib_for(w).qd_clamp_f32(w.data_ptr(), w.numel(), float(limit), _lib.stream_for(w)))
+            lib = _lib.lib_for(w)
+            _lib.check(lib.qd_clamp_f32(w.data_ptr(), w.numel(), float(limit), _lib.stream_for(w)), lib)
         _lib.mark_written(w)               # written through its raw pointer: bump the version counter as clamp_() would
     return weights
 
@@ -52,8 +53,8 @@ def truncated_ste_(grad, weights, limit=1.0):
         raise ValueError('grad and weights must have the same number of elements and live on one device')
     if g.numel():
         with _on(g):
-            _lib.check(_lib.lib_for(g).qd_truncated_ste_f32(w.data_ptr(), g.data_ptr(), g.numel(), float(limit),
-                                                            _lib.stream_for(g)))
+            lib = _lib.lib_for(g)
+            _lib.check(lib.qd_truncated_ste_f32(w.data_ptr(), g.data_ptr(), g.numel(), float(limit), _lib.stream_for(g)), lib)
         _lib.mark_written(g)
     return grad
 
@@ -68,6 +69,7 @@ def ste_bucket_backward(weights, grad, bucket_size, s, out=None, tie_mode='refer
     if bucket_size is None:                                                         # ref: :332-334
         raise NotImplementedError('Right now the code does not work with bucket_size None.'
                                   ' Not hard to modify though')
+    s = _lib.level_count(s)
     given = out is not None
     if out is None:
         out = torch.empty_like(g)
@@ -77,9 +79,10 @@ def ste_bucket_backward(weights, grad, bucket_size, s, out=None, tie_mode='refer
             raise ValueError('out must have as many elements as grad')
     if x.numel():
         with _on(x):
-            _lib.check(_lib.lib_for(x).qd_ste_bucket_backward_f32(
-                x.data_ptr(), g.data_ptr(), out.data_ptr(), x.numel(), int(bucket_size), int(s),
-                0 if tie_mode == 'reference' else 1, _lib.stream_for(x)))
+            lib = _lib.lib_for(x)
+            _lib.check(lib.qd_ste_bucket_backward_f32(
+                x.data_ptr(), g.data_ptr(), out.data_ptr(), x.numel(), int(bucket_size), s,
+                0 if tie_mode == 'reference' else 1, _lib.stream_for(x)), lib)
         if given:
             _lib.mark_written(out)
     return out

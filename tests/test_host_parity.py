@@ -105,6 +105,19 @@ def test_cpu_tensors_never_touch_the_hip_library(monkeypatch):
     ste.clamp_(x.clone(), 1.0)
     ste.truncated_ste_(torch.randn(5000), x, 1.0)
     qhf.initialize_quantization_points(x, quantization.ScalingFunction('linear', False, False, 256), 8)
+    # a host call that is refused says so itself: the error is described by the library that returned it (s = 2^31 does not
+    # fit the C int of the ABI; the Python API refuses it earlier, so it goes through the C ABI here)
+    import ctypes
+    q = torch.full_like(x, 777.0)
+    rc = _lib.host().qd_uniform_f32(x.data_ptr(), q.data_ptr(), x.numel(), 256, ctypes.c_int(2 ** 31), None, None, None, None, 0, 0.0,
+                                    0, 0, None, 0, None)
+    assert rc != 0 and bool((q == 777.0).all())
+    with pytest.raises(RuntimeError, match='qd_host: invalid argument'):
+        _lib.check(rc, _lib.host())
+    with pytest.raises(RuntimeError, match='qd_host: invalid argument'):
+        ste.ste_bucket_backward(x, torch.randn(5000), -5, 16)
+    with pytest.raises(ValueError, match='2\\^31 - 1'):
+        quantization.uniformQuantization(x, 2 ** 31, bucket_size=256)
     # the entry points that exist for device tensors only refuse, loudly
     from quantized_distillation_amd import codec
     from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer
