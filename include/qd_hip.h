@@ -101,7 +101,8 @@ extern "C" {
  * changed meaning).  qd_multi_dq_plan / qd_multi_nearest_f32 / qd_multi_point_grad_f32 take bucket == 0, buckets that are
  * no power of two and k up to 256, also without a bump: arguments that were rejected are now accepted; nothing existing
  * changed meaning.  qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 / qd_multi_ste_backward_levels_f32 (a level
- * count per tensor) are new symbols, likewise without a bump; so are qd_transform_plan and qd_set_grid_cap (host only).
+ * count per tensor) are new symbols, likewise without a bump; so are qd_transform_plan and qd_set_grid_cap (host only), and
+ * qd_multi_uniform_out16_f32 / qd_multi_uniform_global_out16_f32 (fp16 / bf16 outputs).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -342,6 +343,32 @@ int qd_multi_uniform_levels_f32(const QdTensorDesc* table, const int32_t* levels
 int qd_multi_uniform_global_levels_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
                                        int clamp, float max_element, int stochastic, uint64_t seed, const uint64_t* seed_cell,
                                        float* alpha_beta, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Multi-tensor K1 / K1g writing fp16 or bf16 OUTPUTS (fp32 master weights, a 16-bit student): the level-count-per-tensor forms
+ * above with another store.  Device library only.  Tables and tile counts come from qd_multi_plan / qd_multi_global_plan, the
+ * descriptor is QdTensorDesc -- but for these two entry points `q` addresses n 16-BIT elements (out_kind says which format),
+ * needs 2-byte alignment only, and must not overlap any `x` of the table (x stays fp32, 4-byte aligned).
+ *   Contract: element e of tensor i is the IEEE round-to-nearest-even conversion to fp16 / bf16 of element e of what
+ *   qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 writes for the same arguments, bit for bit on the 16-bit
+ *   patterns: a NaN stays a NaN (payload unspecified), +-inf stays, a finite value beyond the format's range becomes +-inf,
+ *   fp16 subnormals are produced (not flushed), the sign of zero is kept.  All arithmetic is the fp32 launch's; only the
+ *   store differs, and the global form's alpha_beta rows have the bits they have there.  Whatever the alignment of q (full
+ *   buckets with x 16-byte and q 8-byte aligned take a register path, everything else a scalar one) the bits are the same,
+ *   and nothing is written before q or from q + n on.
+ *   levels: the device int32 array of qd_multi_uniform_levels_f32, always (one level count for all: equal entries).
+ *   The seed rule, the capture rule, the workspace and total_tiles == 0 (returns 0 without a launch) are those of
+ *   qd_multi_uniform_opt_f32 / qd_multi_uniform_global_opt_f32.
+ *   Errors: out_kind other than the two below, and everything the _levels entry points refuse: QD_ERR_INVALID_ARGUMENT; the
+ *   global form's workspace: QD_ERR_WORKSPACE_TOO_SMALL, nothing written. */
+#define QD_OUT_F16 1
+#define QD_OUT_BF16 2
+int qd_multi_uniform_out16_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                               int64_t bucket, int out_kind, int clamp, float max_element, int stochastic, uint64_t seed,
+                               const uint64_t* seed_cell, void* stream);
+int qd_multi_uniform_global_out16_f32(const QdTensorDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                      int out_kind, int clamp, float max_element, int stochastic, uint64_t seed,
+                                      const uint64_t* seed_cell, float* alpha_beta, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 
 /* Multi-tensor K7: the 'complicated' straight-through backward of every quantized parameter of a model in ONE launch (the
  * per-step loop `quantizeFunctions[idx].backward(p.grad.data)`, cnn_models/conv_forward_model.py:253-266).  `table` is a

@@ -120,6 +120,9 @@ SIGNATURES = {
     'qd_multi_uniform_levels_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_float, c_int, u64, c_p, c_p]),
     'qd_multi_uniform_global_levels_f32': (c_int, [c_p, c_p, c_int, i64, c_int, c_float, c_int, u64, c_p, c_f, c_p, c_size,
                                                    c_p]),
+    'qd_multi_uniform_out16_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_int, c_float, c_int, u64, c_p, c_p]),
+    'qd_multi_uniform_global_out16_f32': (c_int, [c_p, c_p, c_int, i64, c_int, c_int, c_float, c_int, u64, c_p, c_f, c_p, c_size,
+                                                  c_p]),
     'qd_multi_ste_plan': (c_int, [ctypes.POINTER(QdSteDesc), c_int, i64, ctypes.POINTER(ctypes.c_int64)]),
     'qd_multi_ste_backward_f32': (c_int, [c_p, c_int, i64, i64, c_int, c_int, c_p]),
     'qd_multi_ste_backward_levels_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_p]),
@@ -381,6 +384,21 @@ def require_f32(t, what='tensor'):
         raise RuntimeError('quantized_distillation_amd: %s must live on a HIP device or on the CPU (got %s)' % (what, t.device))
     if t.dtype != torch.float32:
         raise TypeError('%s must be float32 (the reference path is fp32-only), got %s' % (what, t.dtype))
+
+
+def require_device_dtype(t, dtype, what='tensor'):
+    """require_device_f32 for dtype float32; a float16 / bfloat16 tensor on a HIP device otherwise (the 16-bit outputs of
+    MultiTensorQuantizer, the only tensors of another type that any entry point takes)."""
+    import torch
+    if dtype == torch.float32:
+        return require_device_f32(t, what)
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (what, type(t)))
+    if not t.is_cuda:
+        raise RuntimeError('quantized_distillation_amd: %s must live on a HIP device (got %s); '
+                           'this entry point has no CPU path' % (what, t.device))
+    if t.dtype != dtype:
+        raise TypeError('%s must be %s, got %s' % (what, dtype, t.dtype))
 
 
 def require_device_f32(t, what='tensor'):

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qd_hip.h"          // QdTensorDesc
+
 namespace qd {
 
 // The last tensor whose prefix field is <= item (a tensor without items is never the answer for an item that exists).
@@ -33,5 +35,15 @@ inline int64_t fill_prefix(Desc* host_table, int ntensors, Count items_of) {
     }
     return total;
 }
+
+// ---- the un-bucketed uniform launches (qd_multi_uniform.hip, qd_multi_uniform_out16.hip) ----
+constexpr int kTile = 1024;     // elements per wave tile: 64 lanes x 4 float4
+
+// Phases 1 and 2 with the clamp limit `me` (+inf: off): k_mg_minmax_opt into part[2 * total_tiles], k_mg_fold into
+// alpha_beta[ntensors][2], on `st`.  Defined next to the kernels in qd_multi_uniform.hip, for the translation unit whose phase 3
+// stores another type: the kernels exist once.  Not part of the C ABI.
+__attribute__((visibility("hidden"))) void launch_mg_minmax_fold(const QdTensorDesc* table, int ntensors, int64_t total_tiles,
+                                                                 float* part, float me, float* alpha_beta, int blocks,
+                                                                 hipStream_t st);
 
 }  // namespace qd

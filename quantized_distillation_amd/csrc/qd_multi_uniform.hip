@@ -186,8 +186,7 @@ __global__ __launch_bounds__(256) void k_multi_uniform_opt(const QdTensorDesc* _
     }
 }
 
-// ---- no buckets ----------------------------------------------------------------------------------
-constexpr int kTile = 1024;     // elements per wave tile: 64 lanes x 4 float4
+// ---- no buckets (kTile, the elements of a wave tile: qd_multi.h) -----------------------------------
 
 // phase 1: per-tile min/max -> part[2*tile], part[2*tile+1]
 __global__ __launch_bounds__(256) void k_mg_minmax(const QdTensorDesc* __restrict__ table, int ntensors, int64_t total_tiles, float* part) {
@@ -532,6 +531,13 @@ inline bool clamp_limit(int clamp, float max_element, float& me) {
 }
 
 }  // namespace
+
+// phases 1 and 2 for qd_multi_uniform_out16.hip (qd_multi.h): the launches of qd_multi_uniform_global_levels_f32 below
+void qd::launch_mg_minmax_fold(const QdTensorDesc* table, int ntensors, int64_t total_tiles, float* part, float me,
+                               float* alpha_beta, int blocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_mg_minmax_opt, dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, part, me);
+    hipLaunchKernelGGL(k_mg_fold, dim3(ntensors), dim3(256), 0, st, table, ntensors, total_tiles, part, alpha_beta);
+}
 
 extern "C" {
 

@@ -44,10 +44,11 @@ class _DeviceTable(object):
     entry_point = None     # name of the C entry point the last launch went through (_entry)
     _WATCH = ()            # attributes holding the tensors a caller may rebind: the table is rebuilt when one of them moved
 
-    def _adopt(self, first_contiguous=True, **named):
+    def _adopt(self, first_contiguous=True, dtypes=None, **named):
         """named[what] = a sequence of tensors, one per tensor of the first sequence.  Returns them as lists of fp32 tensors on
         one HIP device (self.device), each with as many elements as its counterpart in the first list and contiguous (the
-        first list too unless first_contiguous=False: tensors that are only read through a copy)."""
+        first list too unless first_contiguous=False: tensors that are only read through a copy).  dtypes: {what: dtype} for
+        the lists that hold another type than fp32 (the 16-bit outputs of MultiTensorQuantizer)."""
         lists = [list(ts) for ts in named.values()]
         if not lists[0]:
             raise ValueError('no tensors')
@@ -55,7 +56,7 @@ class _DeviceTable(object):
             raise ValueError('%s: need one per tensor' % ', '.join(list(named)[1:]))
         for what, ts in zip(named, lists):
             for t, first in zip(ts, lists[0]):
-                _lib.require_device_f32(t, what)
+                _lib.require_device_dtype(t, (dtypes or {}).get(what, torch.float32), what)
                 if not t.is_contiguous() and (first_contiguous or ts is not lists[0]):
                     raise ValueError('%s must be contiguous' % what)
                 if t.numel() != first.numel():
@@ -137,12 +138,42 @@ class MultiTensorQuantizer(_DeviceTable):
     uniformQuantization(t_i, s[i], ...)); `self.s` keeps the int or a tuple.  A sequence of unequal entries is uploaded once
     as an int32 device array and every option combination launches qd_multi_uniform_levels_f32 /
     qd_multi_uniform_global_levels_f32; a scalar, or a sequence whose entries are all equal, launches what it always
-    launched.  `entry_point` names the C entry point the last quantize() went through."""
+    launched.  `entry_point` names the C entry point the last quantize() went through.
+
+    out_dtype: None (fp32 outputs: everything above, unchanged), torch.float16 or torch.bfloat16 -- fp32 masters quantized
+    straight into a 16-bit model.  `outputs` may then be a list of tensors that are all fp16 or all bf16 (their dtype is
+    enough: out_dtype may stay None), or None to have them allocated.  Element e of outputs[i] is the IEEE round-to-nearest-
+    even conversion of what the fp32 launch writes -- outputs32[i].to(out_dtype), bit for bit -- in the same single launch
+    (qd_multi_uniform_out16_f32; bucket_size=None: qd_multi_uniform_global_out16_f32), without an fp32 shadow and without the
+    cast.  Every option and every form of s goes through that one pair of entry points; the object always owns a levels
+    array.  The inputs stay fp32 and must not overlap the outputs.  `self.out_dtype` keeps the choice (None: fp32)."""
     _DESC = _lib.QdTensorDesc
     _WATCH = ('inputs', 'outputs')
+    _OUT_KINDS = {torch.float16: 1, torch.bfloat16: 2}          # QD_OUT_F16, QD_OUT_BF16 (include/qd_hip.h)
+
+    @classmethod
+    def _output_dtype(cls, outputs, out_dtype):
+        """The outputs' type from `outputs` (None, or a sequence of tensors) and `out_dtype`: None for fp32, else one of the
+        two 16-bit types.  TypeError for anything else, for mixed outputs and for outputs that contradict out_dtype."""
+        if out_dtype is not None and out_dtype != torch.float32 and out_dtype not in cls._OUT_KINDS:
+            raise TypeError('out_dtype must be None, torch.float32, torch.float16 or torch.bfloat16, got %r' % (out_dtype,))
+        have = out_dtype or torch.float32
+        if outputs:
+            for t in outputs:
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError('outputs must be torch.Tensors, got %r' % type(t))
+            kinds = {t.dtype for t in outputs}
+            if len(kinds) > 1:
+                raise TypeError('outputs must all have one dtype, got %s' % ', '.join(sorted(str(k) for k in kinds)))
+            have = kinds.pop()
+            if have != torch.float32 and have not in cls._OUT_KINDS:
+                raise TypeError('outputs must be float32, float16 or bfloat16, got %s' % have)
+            if out_dtype is not None and have != out_dtype:
+                raise TypeError('outputs are %s but out_dtype is %s' % (have, out_dtype))
+        return None if have == torch.float32 else have
 
     def __init__(self, tensors, s, bucket_size, outputs=None, stochastic_rounding=False, max_element=False,
-                 subtract_mean=False, seed_on_device=False):
+                 subtract_mean=False, seed_on_device=False, out_dtype=None):
         if bucket_size is not None and (not isinstance(bucket_size, int) or bucket_size <= 0):
             raise ValueError('bucket_size must be a positive integer or None')
         s, tensors = _level_counts(s, tensors)
@@ -159,12 +190,17 @@ class MultiTensorQuantizer(_DeviceTable):
         self.seed_on_device = bool(seed_on_device)
         self.last_seed = None
         self.seed_cell = None
+        outputs = None if outputs is None else list(outputs)
+        self.out_dtype = self._output_dtype(outputs, out_dtype)
         if outputs is None:
             (self.inputs,) = self._adopt(tensors=tensors)
-            self.outputs = [torch.empty_like(t) for t in self.inputs]
+            self.outputs = [torch.empty_like(t, dtype=self.out_dtype) for t in self.inputs]
         else:
-            self.inputs, self.outputs = self._adopt(tensors=tensors, outputs=outputs)
+            self.inputs, self.outputs = self._adopt(tensors=tensors, outputs=outputs,
+                                                    dtypes={'outputs': self.out_dtype or torch.float32})
         self._bind_levels(s)
+        if self.out_dtype is not None and self._levels is None:     # the 16-bit entry points take the array, always
+            self._levels = torch.full((len(self.inputs),), self._s, dtype=torch.int32, device=self.device)
         self._plan()
         if self.seed_on_device:
             self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -195,6 +231,16 @@ class MultiTensorQuantizer(_DeviceTable):
     def _call_opt(self, seed):
         clamp, me = (0, 0.0) if self.max_element is False else (1, float(self.max_element))
         cell = self.seed_cell.data_ptr() if self.seed_on_device else None
+        if self.out_dtype is not None:             # 16-bit outputs: one pair of entry points for every option and every s
+            kind = self._OUT_KINDS[self.out_dtype]
+            if self.bucket_size is None:
+                return self._entry('qd_multi_uniform_global_out16_f32')(
+                    self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, kind, clamp, me,
+                    int(self.stochastic_rounding), seed, cell, self.alpha_beta.data_ptr(), self._scratch.data_ptr(),
+                    self._scratch.numel() * 4, _lib.stream_ptr(self.device))
+            return self._entry('qd_multi_uniform_out16_f32')(
+                self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, kind, clamp, me,
+                int(self.stochastic_rounding), seed, cell, _lib.stream_ptr(self.device))
         if self._levels is not None:               # a level count per tensor: the one pair of entry points for every option
             if self.bucket_size is None:
                 return self._entry('qd_multi_uniform_global_levels_f32')(
