@@ -102,7 +102,8 @@ extern "C" {
  * no power of two and k up to 256, also without a bump: arguments that were rejected are now accepted; nothing existing
  * changed meaning.  qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 / qd_multi_ste_backward_levels_f32 (a level
  * count per tensor) are new symbols, likewise without a bump; so are qd_transform_plan and qd_set_grid_cap (host only), and
- * qd_multi_uniform_out16_f32 / qd_multi_uniform_global_out16_f32 (fp16 / bf16 outputs).
+ * qd_multi_uniform_out16_f32 / qd_multi_uniform_global_out16_f32 (fp16 / bf16 outputs), and qd_multi_ste_in16_plan /
+ * qd_multi_ste_backward_in16_f32 (fp16 / bf16 gradients).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -399,6 +400,28 @@ int qd_multi_ste_backward_f32(const QdSteDesc* table, int ntensors, int64_t tota
  * wrong values in out_i and touches nothing else. */
 int qd_multi_ste_backward_levels_f32(const QdSteDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
                                      int64_t bucket, int tie_mode, void* stream);
+
+/* Multi-tensor K7 reading fp16 or bf16 GRADIENTS (a 16-bit student's p.grad, fp32 master weights and fp32 master gradients):
+ * qd_multi_ste_backward_levels_f32 with another load.  Device library only.  The descriptor is QdSteDesc -- but for these two
+ * entry points `g` addresses n 16-BIT elements (grad_kind says which format) and needs 2-byte alignment only; x and out stay
+ * fp32, 4-byte aligned; out must not overlap any g or x of the table (no in-place form: the element sizes differ).
+ *   Contract: tensor i equals qd_ste_bucket_backward_f32(x_i, W(g_i), out_i, n_i, bucket, levels[i], tie_mode) bit for bit,
+ *   where W is the exact widening of every element to fp32: fp16 and bf16 subnormals are kept (not flushed), the sign of zero
+ *   is kept, +-inf stays +-inf, a NaN stays a NaN (payload unspecified).  All arithmetic is the fp32 launch's; only the load
+ *   of g differs.  The bits do not depend on the alignment of g: plan and kernel cut a tensor into register tiles and
+ *   single-bucket tiles from n, bucket, x and out alone, so a 2-byte-aligned g takes the register tiles whenever the fp32 call
+ *   on a widened copy would (g is then read with 8-byte loads where it is 8-byte aligned, element by element otherwise).
+ *   That is why the table must be planned by qd_multi_ste_in16_plan, not by qd_multi_ste_plan.
+ *   Nothing is read before g or from g + n on, nothing is written before out or from out + n on.
+ *   levels: the device int32 array of qd_multi_ste_backward_levels_f32, always (one level count for all: equal entries).
+ *   total_tiles == 0 returns 0 without a launch.  No workspace, no allocation, no synchronisation.
+ *   Errors (QD_ERR_INVALID_ARGUMENT, nothing written): grad_kind other than the two below; everything
+ *   qd_multi_ste_backward_levels_f32 refuses; in the plan, what qd_multi_ste_plan refuses and an odd g address. */
+#define QD_GRAD_F16 1
+#define QD_GRAD_BF16 2
+int qd_multi_ste_in16_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out);
+int qd_multi_ste_backward_in16_f32(const QdSteDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                   int64_t bucket, int grad_kind, int tie_mode, void* stream);
 
 /* ---- 'absmax' / 'absnorm' scaling (type_scaling of ScalingFunction, quant_functions.py:109-127,144-146).
  * PARITY UNPINNED: the reference code for these two types raises on every torch version, so these

@@ -126,6 +126,8 @@ SIGNATURES = {
     'qd_multi_ste_plan': (c_int, [ctypes.POINTER(QdSteDesc), c_int, i64, ctypes.POINTER(ctypes.c_int64)]),
     'qd_multi_ste_backward_f32': (c_int, [c_p, c_int, i64, i64, c_int, c_int, c_p]),
     'qd_multi_ste_backward_levels_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_p]),
+    'qd_multi_ste_in16_plan': (c_int, [ctypes.POINTER(QdSteDesc), c_int, i64, ctypes.POINTER(ctypes.c_int64)]),
+    'qd_multi_ste_backward_in16_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_int, c_p]),
     'qd_uniform_abs_f32': (c_int, [c_f, c_f, i64, i64, c_int, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_scale_down_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_inv_scale_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_f, c_f, c_p]),

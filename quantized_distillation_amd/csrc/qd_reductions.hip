@@ -7,6 +7,7 @@
 //   K8  qd_clamp_f32, qd_truncated_ste_f32   the callers' 'truncated' STE     cnn_models/conv_forward_model.py:240-241,263-264
 //   K7m qd_multi_ste_plan, qd_multi_ste_backward_f32  K7 of every parameter in one launch   conv_forward_model.py:253-266
 //       qd_multi_ste_backward_levels_f32              the same with a level count per tensor (k_multi_ste_lv)
+//       qd_multi_ste_in16_plan, qd_multi_ste_backward_in16_f32   the same reading fp16 / bf16 gradients (k_multi_ste_in16)
 // Its own translation unit so that hipcc builds it next to qd_kernels.hip / qd_nearest.hip / qd_scale.hip (parallel build).
 #include "qd_transform.h"      // shared helpers: workspace carving, launch geometry
 #include "qd_multi.h"          // owner_of, fill_prefix for K7m
@@ -672,12 +673,48 @@ __device__ __forceinline__ float ste_term(float g, float q, float x, float aq, f
 // the numerator is >= 0; fabsf keeps the key meaningful should that ever change.
 __device__ __forceinline__ unsigned ste_numerator_key(float x, float bq) { return __float_as_uint(fabsf(x - bq)) - 1u; }
 
+// The gradient's element type G: float (every fp32 entry point; the code below is then what it always was), or _Float16 /
+// __bf16 for qd_multi_ste_backward_in16_f32, which reads 16-bit gradients and widens them on load.  Widening is exact: bf16 is
+// the upper half of the fp32 pattern (an integer shift), fp16 goes through v_cvt_f32_f16 (subnormals kept, not flushed; the
+// sign of zero and +-inf kept; a NaN stays a NaN).  Everything after the load is the fp32 arithmetic, so a launch on 16-bit
+// gradients has the bits of the fp32 launch on a widened copy.
+template <int KIND> struct Grad16;                           // KIND: grad_kind of the C ABI, an int so that kernel names read alike
+template <> struct Grad16<QD_GRAD_F16> { typedef _Float16 type; };
+template <> struct Grad16<QD_GRAD_BF16> { typedef __bf16 type; };
+__device__ __forceinline__ float ste_widen(float g) { return g; }
+__device__ __forceinline__ float ste_widen(_Float16 g) { return (float)g; }
+__device__ __forceinline__ float ste_widen(__bf16 g) {
+    return __uint_as_float((unsigned)__builtin_bit_cast(unsigned short, g) << 16);
+}
+// this lane's four consecutive gradients of the register tile.  16-bit: one 8-byte load where g is 8-byte aligned (p is a
+// multiple of four elements past g: wave-uniform), element by element otherwise; the same lane -> element map either way.
+// (gfx950 under HSA runs with unaligned access allowed, and the compiler knows: it may fuse the four 2-byte loads again.)
+template <typename G>
+__device__ __forceinline__ f4 ste_load_g4(const G* p, bool g8) {
+    if constexpr (std::is_same<G, float>::value) {
+        return __builtin_nontemporal_load((const f4*)p);
+    } else {
+        typedef unsigned short us4 __attribute__((ext_vector_type(4)));
+        us4 h;
+        if (g8) {
+            h = ldg_nt((const us4*)p);
+        } else {
+            const unsigned short* e = (const unsigned short*)p;
+            h.x = ldg_nt(e); h.y = ldg_nt(e + 1); h.z = ldg_nt(e + 2); h.w = ldg_nt(e + 3);
+        }
+        f4 r;
+        r.x = ste_widen(__builtin_bit_cast(G, (unsigned short)h.x)); r.y = ste_widen(__builtin_bit_cast(G, (unsigned short)h.y));
+        r.z = ste_widen(__builtin_bit_cast(G, (unsigned short)h.z)); r.w = ste_widen(__builtin_bit_cast(G, (unsigned short)h.w));
+        return r;
+    }
+}
+
 // vector path: LPB lanes per bucket, V float4 per lane, the whole bucket (x, g, q) in registers, one pass.  Index ties:
 // the FIRST element (in memory order) at the top / bottom level of the quantized bucket (or the true arg of x).
 // One tile (= one wave iteration, 64 / LPB buckets) of the vector path: the body of k_ste_backward_vec and of the register
 // tiles of k_multi_ste, so that both sum a bucket in the same order.
-template <int LPB, int V>
-__device__ __forceinline__ void ste_vec_tile(const float* x, const float* g, float* out, int64_t nvec, int64_t t, int sub, int l,
+template <int LPB, int V, typename G = float>
+__device__ __forceinline__ void ste_vec_tile(const float* x, const G* g, float* out, int64_t nvec, int64_t t, int sub, int l,
                                              float sm1, int tie_mode, bool use_tab, float tab) {
     constexpr int BPW = 64 / LPB;                            // sub = lane / LPB: the bucket of the tile, l = lane % LPB
     constexpr int ROW = LPB * V * 4;
@@ -686,10 +723,11 @@ __device__ __forceinline__ void ste_vec_tile(const float* x, const float* g, flo
         if (bkt >= nvec) return;
         const int64_t e0 = bkt * ROW + (int64_t)l * 4;
         f4 xv[V], gv[V], qv[V];
+        const bool g8 = (((uintptr_t)g) & 7) == 0;          // (16-bit gradients only)
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             xv[j] = __builtin_nontemporal_load((const f4*)(x + e0) + j * LPB);
-            gv[j] = __builtin_nontemporal_load((const f4*)(g + e0) + j * LPB);
+            gv[j] = ste_load_g4(g + e0 + j * LPB * 4, g8);
         }
         // NaN-propagating, as torch's min / max and as the forward kernel: a bucket that holds a NaN (or an infinity: alpha =
         // inf) quantizes to NaN as a whole, its sum S is NaN, and the reference adds and subtracts S at the FIRST NaN -- the
@@ -791,7 +829,8 @@ __global__ __launch_bounds__(256) void k_ste_backward_vec(const float* x, const 
 
 // any bucket size / alignment: one wave per bucket, four passes over the (L1/L2-resident) bucket.  The body of k_ste_backward
 // and of the generic tiles of k_multi_ste.
-__device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, float* out, int64_t n, int64_t row, int64_t bkt,
+template <typename G = float>
+__device__ __forceinline__ void ste_wave_bucket(const float* x, const G* g, float* out, int64_t n, int64_t row, int64_t bkt,
                                                 int lane, float sm1, int tie_mode) {
     {
         const int64_t lo = bkt * row;
@@ -830,7 +869,7 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, 
                 float lev;
                 const float xv = x[i];
                 const float q = qdq(xv, a, b, sm1, 0.0f, lev);
-                s += ste_term<FAST>(g[i], q, xv, aq, bq, yq);
+                s += ste_term<FAST>(ste_widen(g[i]), q, xv, aq, bq, yq);
                 const float sv = tie_mode == QD_STE_TIE_REFERENCE ? q : xv;
                 const bool top = bad ? (sv != sv) : (sv == (tie_mode == QD_STE_TIE_REFERENCE ? qmx : mx));
                 const bool bot = bad ? (sv != sv) : (sv == (tie_mode == QD_STE_TIE_REFERENCE ? qmn : mn));
@@ -844,7 +883,7 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const float* g, 
         jmin = wave_min_ll(jmin);
         // pass 4: out = g, +S at jmax, -S at jmin (they cancel when the bucket is constant)
         for (int64_t i = lo + lane; i < hi; i += 64) {
-            float o = g[i];
+            float o = ste_widen(g[i]);
             if (jmax != jmin || bad) {                     // (a NaN bucket: (g + S) - S = NaN at the first NaN, as the reference)
                 if (i == jmax) o = o + s;
                 if (i == jmin) o = o - s;
@@ -1017,6 +1056,44 @@ __global__ __launch_bounds__(256) void k_multi_ste_lv(const QdSteDesc* __restric
         } else {
             const int64_t bkt = c.nfull + (local - c.vtiles);   // (a tile count that does not belong to this table reaches no bucket)
             if (local >= 0 && bkt * c.row < d.n) ste_wave_bucket(d.x, d.g, d.out, d.n, c.row, bkt, lane, sm1, tie_mode);
+        }
+    }
+}
+
+// k_multi_ste_lv reading 16-bit gradients (qd_multi_ste_backward_in16_f32): d.g addresses n fp16 / bf16 elements, x and out stay
+// fp32, out never aliases g.  The same tile loop and the same two bodies, instantiated for the gradient's type.  The cut is made
+// from n, bucket, x and out alone (no g goes to ste_cut) -- g's alignment must not decide which body sums a bucket -- which is
+// what qd_multi_ste_in16_plan counted.
+template <int LPB, int V, int KIND>
+__global__ __launch_bounds__(256) void k_multi_ste_in16(const QdSteDesc* __restrict__ table, const int32_t* __restrict__ levels,
+                                                        int ntensors, int64_t total_tiles, int64_t bucket, int tie_mode) {
+    typedef typename Grad16<KIND>::type G;
+    constexpr int ROW = LPB * V * 4;                  // 0: no register path at this bucket size
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    int cur = -1;                                   // the tensor sm1 / use_tab / tab below belong to
+    float sm1 = 1.0f, tab = 0.0f;
+    bool use_tab = false;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdSteDesc d = table[ti];                                  // (an empty tensor owns no tile)
+        if (d.n <= 0) continue;
+        if (ti != cur) {
+            cur = ti;
+            sm1 = (float)(levels[ti] - 1);
+            use_tab = sm1 <= 15.0f;
+            tab = (float)(lane & 15) / sm1;
+        }
+        const int64_t local = t - d.first_tile;
+        const G* const g = (const G*)d.g;
+        const SteCut c = ste_cut<ROW>(d.x, nullptr, d.out, d.n, bucket);
+        if (local < c.vtiles) {
+            if constexpr (LPB > 0) ste_vec_tile<LPB, V, G>(d.x, g, d.out, c.nfull, local, lane / LPB, lane % LPB, sm1, tie_mode,
+                                                            use_tab, tab);
+        } else {
+            const int64_t bkt = c.nfull + (local - c.vtiles);   // (a tile count that does not belong to this table reaches no bucket)
+            if (local >= 0 && bkt * c.row < d.n) ste_wave_bucket<G>(d.x, g, d.out, d.n, c.row, bkt, lane, sm1, tie_mode);
         }
     }
 }
@@ -1267,6 +1344,48 @@ int qd_multi_ste_backward_levels_f32(const QdSteDesc* table, const int32_t* leve
     if (!ste_lanes_per_bucket(bucket))
         hipLaunchKernelGGL((k_multi_ste_lv<0, 0>), dim3(blocks), dim3(256), 0, st, table, levels, ntensors, total_tiles, bucket,
                            tie_mode);
+    return check_launch();
+}
+
+
+int qd_multi_ste_in16_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out) {
+    if (!host_table || ntensors <= 0 || bucket <= 0 || !total_tiles_out) return QD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < ntensors; ++i) {
+        const QdSteDesc& d = host_table[i];
+        if (d.n < 0 || (d.n > 0 && (!d.x || !d.g || !d.out || (((uintptr_t)d.g) & 1)))) return QD_ERR_INVALID_ARGUMENT;
+    }
+    *total_tiles_out = fill_prefix(host_table, ntensors, [bucket](const QdSteDesc& d) -> int64_t {
+        if (d.n <= 0) return 0;
+        const SteCut c = ste_cut(d.x, nullptr, d.out, d.n, bucket);     // g's alignment has no say (k_multi_ste_in16)
+        return c.vtiles + (c.nb - c.nfull);
+    });
+    return 0;
+}
+
+int qd_multi_ste_backward_in16_f32(const QdSteDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
+                                   int64_t bucket, int grad_kind, int tie_mode, void* stream) {
+    if (!table || !levels || (((uintptr_t)levels) & 3) || ntensors <= 0 || total_tiles < 0 || bucket <= 0)
+        return QD_ERR_INVALID_ARGUMENT;
+    if (tie_mode != QD_STE_TIE_REFERENCE && tie_mode != QD_STE_TIE_TRUE_ARG) return QD_ERR_INVALID_ARGUMENT;
+    if (grad_kind != QD_GRAD_F16 && grad_kind != QD_GRAD_BF16) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = blocks_for(total_tiles, 4);
+#define QD_MULTI_STE_IN16_KIND(LPB, V, KIND)                                                                             \
+    hipLaunchKernelGGL((k_multi_ste_in16<LPB, V, KIND>), dim3(blocks), dim3(256), 0, st, table, levels, ntensors,         \
+                       total_tiles, bucket, tie_mode)
+#define QD_MULTI_STE_IN16(ROW, LPB, V)                                                                                   \
+    if (bucket == ROW) {                                                                                                 \
+        if (grad_kind == QD_GRAD_F16) QD_MULTI_STE_IN16_KIND(LPB, V, QD_GRAD_F16);                                       \
+        else QD_MULTI_STE_IN16_KIND(LPB, V, QD_GRAD_BF16);                                                               \
+    }
+    QD_STE_SHAPES(QD_MULTI_STE_IN16)
+    if (!ste_lanes_per_bucket(bucket)) {
+        if (grad_kind == QD_GRAD_F16) QD_MULTI_STE_IN16_KIND(0, 0, QD_GRAD_F16);
+        else QD_MULTI_STE_IN16_KIND(0, 0, QD_GRAD_BF16);
+    }
+#undef QD_MULTI_STE_IN16
+#undef QD_MULTI_STE_IN16_KIND
     return check_launch();
 }
 

@@ -48,7 +48,8 @@ class _DeviceTable(object):
         """named[what] = a sequence of tensors, one per tensor of the first sequence.  Returns them as lists of fp32 tensors on
         one HIP device (self.device), each with as many elements as its counterpart in the first list and contiguous (the
         first list too unless first_contiguous=False: tensors that are only read through a copy).  dtypes: {what: dtype} for
-        the lists that hold another type than fp32 (the 16-bit outputs of MultiTensorQuantizer)."""
+        the lists that hold another type than fp32 (the 16-bit outputs of MultiTensorQuantizer, the 16-bit gradients of
+        MultiTensorSTE)."""
         lists = [list(ts) for ts in named.values()]
         if not lists[0]:
             raise ValueError('no tensors')
@@ -382,9 +383,29 @@ class MultiTensorSTE(_DeviceTable):
     s: one level count, or a sequence with one entry per tensor (s[i] in the call above), as MultiTensorQuantizer takes it:
     unequal entries launch qd_multi_ste_backward_levels_f32, anything else the entry point above (`entry_point` names the one
     the last backward() took).
+
+    grads may instead be all torch.float16 or all torch.bfloat16 -- the p.grad of a 16-bit student over fp32 masters.
+    `weights` stay fp32 and `outs` is a list of fp32 tensors (outs=None: allocated, one per gradient; there is no in-place form,
+    the element sizes differ) that must not overlap the gradients or the weights.  Each result is bit-identical to the fp32
+    object's on grads[i].float() -- the widening is exact and happens inside the one launch (qd_multi_ste_in16_plan,
+    qd_multi_ste_backward_in16_f32), whatever the alignment of the gradients.  Every form of s goes through that entry point;
+    the object always owns a levels array.  `self.grad_dtype` keeps the 16-bit type (None: fp32 gradients, which plan and
+    launch what they always did).
     """
     _DESC = _lib.QdSteDesc
     _WATCH = ('weights', 'grads', 'outs')
+    _GRAD_KINDS = {torch.float16: 1, torch.bfloat16: 2}         # QD_GRAD_F16, QD_GRAD_BF16 (include/qd_hip.h)
+
+    @classmethod
+    def _gradient_dtype(cls, grads):
+        """None for fp32 gradients (and for whatever the fp32 path refuses itself), else the one 16-bit type of all of them.
+        TypeError for 16-bit gradients mixed with anything else."""
+        kinds = {t.dtype for t in grads if isinstance(t, torch.Tensor)}
+        if not kinds & set(cls._GRAD_KINDS):
+            return None
+        if len(kinds) > 1 or not all(isinstance(t, torch.Tensor) for t in grads):
+            raise TypeError('grads must all have one dtype, got %s' % ', '.join(sorted(str(k) for k in kinds)))
+        return kinds.pop()
 
     def __init__(self, weights, grads, s, bucket_size, outs=None, tie_mode='reference'):
         if bucket_size is None:                                                         # ref: quant_functions.py:332-334
@@ -397,13 +418,24 @@ class MultiTensorSTE(_DeviceTable):
             raise ValueError("tie_mode must be 'reference' or 'true_arg'")
         self.bucket_size = bucket_size
         self.tie_mode = 0 if tie_mode == 'reference' else 1
+        grads = list(grads)
+        self.grad_dtype = self._gradient_dtype(grads)
         # OWNING references: the device table holds raw pointers into these tensors
-        if outs is None:
+        if self.grad_dtype is not None:
+            if outs is None:
+                self.weights, self.grads = self._adopt(weights=weights, grad=grads, dtypes={'grad': self.grad_dtype})
+                self.outs = [torch.empty(g.shape, dtype=torch.float32, device=g.device) for g in self.grads]
+            else:
+                self.weights, self.grads, self.outs = self._adopt(weights=weights, grad=grads, out=outs,
+                                                                  dtypes={'grad': self.grad_dtype})
+        elif outs is None:
             self.weights, self.grads = self._adopt(weights=weights, grad=grads)
             self.outs = self.grads
         else:
             self.weights, self.grads, self.outs = self._adopt(weights=weights, grad=grads, out=outs)
         self._bind_levels(s)
+        if self.grad_dtype is not None and self._levels is None:    # the 16-bit entry point takes the array, always
+            self._levels = torch.full((len(self.weights),), self._s, dtype=torch.int32, device=self.device)
         self._plan()
 
     def _columns(self):
@@ -411,11 +443,16 @@ class MultiTensorSTE(_DeviceTable):
 
     def _plan_table(self, host, n):
         tiles = ctypes.c_int64(0)
-        _lib.check(_lib.load().qd_multi_ste_plan(host, n, self.bucket_size, ctypes.byref(tiles)))
+        plan = _lib.load().qd_multi_ste_plan if self.grad_dtype is None else _lib.load().qd_multi_ste_in16_plan
+        _lib.check(plan(host, n, self.bucket_size, ctypes.byref(tiles)))
         return int(tiles.value)
 
     def backward(self, check_pointers=True):
         """out = the bucket-aware STE gradient for every tensor (one launch).  Returns the list of outs."""
+        if self.grad_dtype is not None:
+            return self._launch(lambda: self._entry('qd_multi_ste_backward_in16_f32')(
+                self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size,
+                self._GRAD_KINDS[self.grad_dtype], self.tie_mode, _lib.stream_ptr(self.device)), self.outs, check_pointers)
         if self._levels is not None:
             return self._launch(lambda: self._entry('qd_multi_ste_backward_levels_f32')(
                 self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.tie_mode,
