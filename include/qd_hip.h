@@ -103,7 +103,8 @@ extern "C" {
  * changed meaning.  qd_multi_uniform_levels_f32 / qd_multi_uniform_global_levels_f32 / qd_multi_ste_backward_levels_f32 (a level
  * count per tensor) are new symbols, likewise without a bump; so are qd_transform_plan and qd_set_grid_cap (host only), and
  * qd_multi_uniform_out16_f32 / qd_multi_uniform_global_out16_f32 (fp16 / bf16 outputs), and qd_multi_ste_in16_plan /
- * qd_multi_ste_backward_in16_f32 (fp16 / bf16 gradients).
+ * qd_multi_ste_backward_in16_f32 (fp16 / bf16 gradients), and qd_multi_nearest_out16_f32 / qd_multi_point_grad_in16_f32 (the
+ * differentiable-quantization sweeps with fp16 / bf16 outputs and gradients; qd_multi_dq_plan now refuses an odd q or grad).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -452,11 +453,11 @@ int qd_inv_scale_abs_f32(const float* u, const float* sign, float* y, int64_t n,
  * per element, a float4 can straddle a bucket end). */
 typedef struct QdDiffQuantDesc {
     const float* u;       /* scaled weights, resident [n]                                  */
-    float* q;             /* quantized weights out [n]                                     */
+    float* q;             /* quantized weights out [n] (qd_multi_nearest_out16_f32: n 16-bit elements)   */
     uint8_t* idx;         /* point index out (forward) / in (backward) [n]                 */
     const float* alpha;   /* [num_buckets]                                                 */
     const float* beta;    /* [num_buckets]                                                 */
-    const float* grad;    /* dLoss/dq [n] (backward only)                                  */
+    const float* grad;    /* dLoss/dq [n] (backward only; qd_multi_point_grad_in16_f32: n 16-bit elements) */
     int64_t n;
     int64_t first_tile;   /* filled by qd_multi_dq_plan: prefix of forward tiles (4 buckets; bucket == 0: 1024 elements) */
     int64_t first_block;  /* filled by qd_multi_dq_plan: prefix of FULL 1024-element gradient tiles (backward) */
@@ -475,6 +476,44 @@ int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t tot
  * at most (2048 + 1) KiB ~ 2 MiB per tensor (WRN-16-22, 60 tensors: 21001 rows = 21.5 MB) */
 int qd_multi_point_grad_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k,
                             float* grad_points, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The two sweeps for a 16-BIT STUDENT over fp32 masters: fp16 / bf16 quantized weights out, fp16 / bf16 gradients in.  Device
+ * library only.  Both take the QdDiffQuantDesc table and the tile / row counts of qd_multi_dq_plan (the plan depends on no
+ * pointer); u, alpha, beta, idx, points and grad_points are what they are above, fp32.  The two are independent: a table may
+ * hold 16-bit q with fp32 grad or the reverse, each field read by the entry point that matches it.
+ *
+ * qd_multi_nearest_out16_f32: `q` addresses n 16-BIT elements (out_kind: QD_OUT_F16 / QD_OUT_BF16), needs 2-byte alignment
+ *   only and must not overlap any `u`.
+ *   Contract: element e of tensor i is the IEEE round-to-nearest-even conversion to fp16 / bf16 of what qd_multi_nearest_f32
+ *   writes for the same arguments, bit for bit on the 16-bit pattern: a NaN stays a NaN (payload unspecified), +-inf stays, a
+ *   finite value beyond the format's range becomes +-inf, fp16 subnormals are produced (not flushed), the sign of zero is
+ *   kept.  idx is byte-identical to the fp32 launch's.  k, bucket (0 or any positive size) and the NaN rule (a NaN u takes
+ *   k - 1) are those of qd_multi_nearest_f32.  The bits do not depend on the alignment of q (full buckets -- bucket 0: full
+ *   1024-element tiles -- with u 16-byte, q 8-byte and idx 4-byte aligned take a register path that stores four values with one
+ *   8-byte store, everything else goes element by element), and nothing is written before q or from q + n on.
+ *   Errors (QD_ERR_INVALID_ARGUMENT, nothing written): what qd_multi_nearest_f32 refuses, and an out_kind other than the two.
+ *
+ * qd_multi_point_grad_in16_f32: `grad` addresses n 16-BIT elements (grad_kind: QD_GRAD_F16 / QD_GRAD_BF16) and needs 2-byte
+ *   alignment only.
+ *   Contract: row i of grad_points equals, bit for bit, what qd_multi_point_grad_f32 gives with grad_i replaced by its exact
+ *   fp32 widening held at a 16-byte-aligned address (subnormals, -0, +-inf and NaN are kept by the widening); everything else
+ *   is the same, the second stage included.  The alignment of the 16-bit gradient has no say in the summation order: where
+ *   the fp32 kernel picks between a lane that owns four consecutive elements and a lane-strided element-wise walk from grad's
+ *   alignment (the two sum in different orders), this one takes the four-consecutive assignment whenever idx is 4-byte aligned
+ *   -- reading grad with 8-byte loads where it is 8-byte aligned and with narrower loads otherwise -- and the strided walk
+ *   only with a misaligned idx, as the fp32 launch does; in the main grid and in the extra waves alike.  Nothing is read
+ *   before grad or from grad + n on.
+ *   Workspace, the checks on total_blocks and the error codes are those of qd_multi_point_grad_f32; a grad_kind other than the
+ *   two: QD_ERR_INVALID_ARGUMENT.
+ *
+ * Odd addresses: the launches take a DEVICE table and cannot look into it without a synchronisation, so the pointers are
+ * checked where the host sees them: qd_multi_dq_plan returns -1 (QD_ERR_INVALID_ARGUMENT), with no field written, when q or
+ * grad of a tensor that has elements is odd -- wrong for fp32 and for 16-bit elements alike. */
+int qd_multi_nearest_out16_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles, int64_t bucket,
+                               const float* points, int k, int out_kind /* QD_OUT_F16 | QD_OUT_BF16 */, void* stream);
+int qd_multi_point_grad_in16_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k,
+                                 int grad_kind /* QD_GRAD_F16 | QD_GRAD_BF16 */, float* grad_points, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 /* ---- packed-index codec (the compressed form whose SIZE the reference accounts for in
  * helpers/functions.py:226-262: bits*N/8 bytes of level indices + 8 bytes (alpha, beta) per

@@ -134,6 +134,8 @@ SIGNATURES = {
     'qd_multi_dq_plan': (i64, [ctypes.POINTER(QdDiffQuantDesc), c_int, i64, ctypes.POINTER(ctypes.c_int64)]),
     'qd_multi_nearest_f32': (c_int, [c_p, c_int, i64, i64, c_f, c_int, c_p]),
     'qd_multi_point_grad_f32': (c_int, [c_p, c_int, i64, i64, c_int, c_f, c_p, c_size, c_p]),
+    'qd_multi_nearest_out16_f32': (c_int, [c_p, c_int, i64, i64, c_f, c_int, c_int, c_p]),
+    'qd_multi_point_grad_in16_f32': (c_int, [c_p, c_int, i64, i64, c_int, c_int, c_f, c_p, c_size, c_p]),
     'qd_packed_bytes': (i64, [i64, c_int]),
     'qd_pack_uniform_f32': (c_int, [c_f, i64, i64, c_int, c_int, c_p, c_f, c_f, c_p]),
     'qd_pack_levels_u8': (c_int, [c_p, i64, c_int, c_p, c_p]),

@@ -7,6 +7,9 @@
 // With 60 tensors that is 120+ kernel launches per step from Python; the two entry points here
 // do each sweep in ONE launch over a device table of per-tensor descriptors.  Arithmetic is
 // identical to qd_nearest_point_f32(prescaled, QD_ASSIGN_MIDPOINT) / qd_point_grad_f32.
+//   qd_multi_nearest_f32, qd_multi_point_grad_f32             fp32 outputs / gradients
+//   qd_multi_nearest_out16_f32, qd_multi_point_grad_in16_f32  fp16 / bf16 outputs / gradients (a 16-bit student over fp32 masters):
+//                                                             the same bodies instantiated on the element type
 #include "qd_common.h"
 #include "qd_multi.h"
 #include "../../include/qd_hip.h"
@@ -57,16 +60,33 @@ __device__ __forceinline__ uint32_t nearest4(const float* pts, const float* mid,
     return i0 | (i1 << 8) | (i2 << 16) | (i3 << 24);
 }
 
+// The store type Q of the forward sweep: float (qd_multi_nearest_f32; the code is then what it always was) or _Float16 / __bf16
+// (qd_multi_nearest_out16_f32: d.q addresses n 16-bit elements).  Every fp32 operation is the same; the fp32 result is converted
+// by the compiler's own conversion (IEEE round to nearest even) in the store.  The register path wants u 16-byte aligned, idx
+// 4-byte aligned, and q aligned for one store of four results per lane: 16 bytes for fp32, 8 bytes for 16-bit.
+template <typename Q> constexpr uintptr_t q_fast_mask() { return sizeof(Q) == 4 ? 15 : 7; }
+template <typename Q> struct Vec4 { typedef Q type __attribute__((ext_vector_type(4))); };      // a lane's four consecutive elements
+template <typename Q>
+__device__ __forceinline__ void store_q4(const f4& r, typename Vec4<Q>::type* dst) {
+    if constexpr (std::is_same<Q, float>::value) stg_nt(r, dst);
+    else store4_nt(r, (Q*)dst);
+}
+
+// block_dim: blockDim.x, read by the kernel (a device function reads it the slow way, through the partial-work-group check)
+__device__ __forceinline__ int64_t uniform_wave_index(unsigned block_dim) {
+    return (int64_t)blockIdx.x * (block_dim >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
 // forward: a tile = 4 buckets of one tensor = one wave iteration; a DPP row owns a bucket
-template <int ROW>
-__global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __restrict__ table, int ntensors, int64_t total_tiles,
-                                                       int64_t bucket, const float* points, int k) {
+template <int ROW, typename Q>
+__device__ __forceinline__ void multi_nearest(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles,
+                                              int64_t bucket, const float* points, int k, unsigned block_dim) {
     __shared__ float s_pts[4][kMaxK];
     __shared__ float s_mid[4][kMaxK];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int sub = lane >> 4, l = lane & 15;
-    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = uniform_wave_index(block_dim);      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * block_dim) >> 6;
     for (int64_t t = wave; t < total_tiles; t += nwaves) {
         const int ti = owner_of(table, ntensors, t);                   // wave-uniform
         const QdDiffQuantDesc d = table[ti];
@@ -78,12 +98,13 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
         const int64_t lo = bkt * row;
         const int64_t hi = lo + row < d.n ? lo + row : d.n;
         const float a = ldg(d.alpha + bkt), b = ldg(d.beta + bkt);
-        const bool fast = ROW > 0 && (hi - lo) == ROW &&
-                          (((((uintptr_t)d.u) | ((uintptr_t)d.q)) & 15) == 0) && ((((uintptr_t)d.idx) & 3) == 0);
+        Q* const qo = (Q*)d.q;                                          // n elements of the store type (include/qd_hip.h)
+        const bool fast = ROW > 0 && (hi - lo) == ROW && ((((uintptr_t)d.u) & 15) | (((uintptr_t)d.q) & q_fast_mask<Q>())) == 0 &&
+                          ((((uintptr_t)d.idx) & 3) == 0);
         if (fast) {
             constexpr int V = ROW > 0 ? ROW / 64 : 1;
             const f4* src = (const f4*)(d.u + lo) + l;
-            f4* dst = (f4*)(d.q + lo) + l;
+            typename Vec4<Q>::type* dst = (typename Vec4<Q>::type*)(qo + lo) + l;
             f4 v[V];
 #pragma unroll
             for (int j = 0; j < V; ++j) v[j] = ldg_nt(src + j * 16);
@@ -91,18 +112,31 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
             for (int j = 0; j < V; ++j) {
                 f4 r;
                 const uint32_t pk = nearest4(s_pts[w], s_mid[w], k, v[j], a, b, r);
-                stg_nt(r, dst + j * 16);
+                store_q4<Q>(r, dst + j * 16);
                 stg(pk, (uint32_t*)(d.idx + lo + ((int64_t)(j * 16 + l) << 2)));
             }
         } else {
             for (int64_t i = lo + l; i < hi; i += 16) {
                 float q;
                 const int id = nearest1(s_pts[w], s_mid[w], k, d.u[i], a, b, q);
-                d.q[i] = q;
+                qo[i] = (Q)q;
                 d.idx[i] = (uint8_t)id;
             }
         }
     }
+}
+
+template <int ROW>
+__global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __restrict__ table, int ntensors, int64_t total_tiles,
+                                                       int64_t bucket, const float* points, int k) {
+    multi_nearest<ROW, float>(table, ntensors, total_tiles, bucket, points, k, blockDim.x);
+}
+
+// OUT: the out_kind of the C ABI
+template <int ROW, int OUT>
+__global__ __launch_bounds__(256) void k_multi_nearest_o16(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                           int64_t total_tiles, int64_t bucket, const float* points, int k) {
+    multi_nearest<ROW, typename Out16<OUT>::type>(table, ntensors, total_tiles, bucket, points, k, blockDim.x);
 }
 
 // forward without buckets (bucket == 0): a tile = kFlatTile consecutive elements of one tensor = one wave iteration, all under
@@ -111,13 +145,14 @@ __global__ __launch_bounds__(256) void k_multi_nearest(const QdDiffQuantDesc* __
 // not 16-byte or whose idx is not 4-byte aligned, go element by element.
 constexpr int kFlatTile = 1024;
 
-__global__ __launch_bounds__(256) void k_multi_nearest_flat(const QdDiffQuantDesc* __restrict__ table, int ntensors,
-                                                            int64_t total_tiles, const float* points, int k) {
+template <typename Q>
+__device__ __forceinline__ void multi_nearest_flat(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles,
+                                                   const float* points, int k, unsigned block_dim) {
     __shared__ float s_pts[4][kMaxK];
     __shared__ float s_mid[4][kMaxK];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t wave = uniform_wave_index();
-    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t wave = uniform_wave_index(block_dim);
+    const int64_t nwaves = ((int64_t)gridDim.x * block_dim) >> 6;
     for (int64_t t = wave; t < total_tiles; t += nwaves) {
         const int ti = owner_of(table, ntensors, t);                   // wave-uniform
         const QdDiffQuantDesc d = table[ti];
@@ -125,11 +160,12 @@ __global__ __launch_bounds__(256) void k_multi_nearest_flat(const QdDiffQuantDes
         const int64_t lo = (t - d.first_tile) * kFlatTile;
         const int64_t hi = lo + kFlatTile < d.n ? lo + kFlatTile : d.n;
         const float a = ldg(d.alpha), b = ldg(d.beta);
-        const bool fast = (hi - lo) == kFlatTile &&
-                          (((((uintptr_t)d.u) | ((uintptr_t)d.q)) & 15) == 0) && ((((uintptr_t)d.idx) & 3) == 0);
+        Q* const qo = (Q*)d.q;
+        const bool fast = (hi - lo) == kFlatTile && ((((uintptr_t)d.u) & 15) | (((uintptr_t)d.q) & q_fast_mask<Q>())) == 0 &&
+                          ((((uintptr_t)d.idx) & 3) == 0);
         if (fast) {
             const f4* src = (const f4*)(d.u + lo) + lane;
-            f4* dst = (f4*)(d.q + lo) + lane;
+            typename Vec4<Q>::type* dst = (typename Vec4<Q>::type*)(qo + lo) + lane;
             uint32_t* ix = (uint32_t*)(d.idx + lo) + lane;
             f4 v[4];
 #pragma unroll
@@ -138,18 +174,29 @@ __global__ __launch_bounds__(256) void k_multi_nearest_flat(const QdDiffQuantDes
             for (int j = 0; j < 4; ++j) {
                 f4 r;
                 const uint32_t pk = nearest4(s_pts[w], s_mid[w], k, v[j], a, b, r);
-                stg_nt(r, dst + j * 64);
+                store_q4<Q>(r, dst + j * 64);
                 stg(pk, ix + j * 64);
             }
         } else {
             for (int64_t i = lo + lane; i < hi; i += 64) {
                 float q;
                 const int id = nearest1(s_pts[w], s_mid[w], k, d.u[i], a, b, q);
-                d.q[i] = q;
+                qo[i] = (Q)q;
                 d.idx[i] = (uint8_t)id;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_multi_nearest_flat(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                            int64_t total_tiles, const float* points, int k) {
+    multi_nearest_flat<float>(table, ntensors, total_tiles, points, k, blockDim.x);
+}
+
+template <int OUT>
+__global__ __launch_bounds__(256) void k_multi_nearest_flat_o16(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                                int64_t total_tiles, const float* points, int k) {
+    multi_nearest_flat<typename Out16<OUT>::type>(table, ntensors, total_tiles, points, k, blockDim.x);
 }
 
 // ---- backward: grad of the points of every tensor, one launch + one fold --------------------------------------------
@@ -198,10 +245,18 @@ __device__ __forceinline__ int owner_of_tile(const QdDiffQuantDesc* table, int n
 // tile -> wave -> row assignment is that of the 2048 waves whatever a block holds of them, so the fold does not change.
 // DIV: the bucket is not a power of two -- the alpha of element e is alpha[e / bucket], looked up per element (a float4 can
 // straddle a bucket end); otherwise alpha[e >> row_shift], one per float4.  Functional, not tuned.
-template <int KR, int WPB, bool DIV>
-__global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuantDesc* __restrict__ table, int ntensors,
-                                                               int64_t bucket, int row_shift, int k, float* part /* [rows][k] */) {
+// G: the gradient's element type -- float (qd_multi_point_grad_f32; the code is then what it always was) or _Float16 / __bf16
+// (qd_multi_point_grad_in16_f32: d.grad addresses n 16-bit elements, widened exactly on load).  Only the load differs: the one
+// fp32 multiply g alpha, the bins, the flush order and the rows are the same.  With 16-bit gradients the alignment of grad has no
+// say in the summation order: a lane owns four consecutive elements whenever idx is 4-byte aligned (grad is read with 8-byte
+// loads where it is 8-byte aligned -- a tile starts a multiple of 2 KiB into the tensor, a lane's four a multiple of 8 bytes into
+// the tile -- and element by element otherwise), so the sums are those of the fp32 launch on a 16-byte-aligned widened copy.
+template <int KR, int WPB, bool DIV, typename G>
+__device__ __forceinline__ void multi_point_grad(const QdDiffQuantDesc* table, int ntensors, int64_t bucket,
+                                                 int row_shift, int k, float* part /* [rows][k] */) {
     extern __shared__ __attribute__((aligned(16))) float lds[];        // KR == 0: [k][64 WPB]
+    constexpr bool G32 = std::is_same<G, float>::value;
+    typedef G G4 __attribute__((ext_vector_type(4)));                  // a lane's four consecutive gradients: 16 or 8 bytes
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     constexpr int C = 64 * WPB;                                        // columns = lanes of a block
@@ -284,7 +339,12 @@ __global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuant
     auto scalar_span = [&](const QdDiffQuantDesc& d, int64_t lo, int64_t hi) {        // element by element (a view at an odd offset)
         const bool single = d.n <= bucket;
         for (int64_t e = lo + lane; e < hi; e += 64)
-            add((int)d.idx[e], d.grad[e] * d.alpha[single ? 0 : bucket_of(e)]);
+            add((int)d.idx[e], widen(((const G*)d.grad)[e]) * d.alpha[single ? 0 : bucket_of(e)]);
+    };
+    // a lane's four consecutive gradients (all four exist).  g8: the tensor's grad is 8-byte aligned (16-bit gradients only)
+    auto load4 = [&](const G4* p, bool g8) -> f4 {
+        if constexpr (G32) return ldg_nt(p);
+        else return load16x4_nt((const G*)p, g8);
     };
 
     if ((int)blockIdx.x >= B) {
@@ -297,30 +357,31 @@ __global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuant
         clear();
         const int64_t e0 = d.n - rem;
         const bool single = d.n <= bucket;
-        const bool aligned = ((((uintptr_t)d.grad) & 15) == 0) && ((((uintptr_t)d.idx) & 3) == 0);
+        const bool aligned = (!G32 || ((((uintptr_t)d.grad) & 15) == 0)) && ((((uintptr_t)d.idx) & 3) == 0);
+        const bool g8 = (((uintptr_t)d.grad) & 7) == 0;
         if (aligned) {
             // every lane issues its loads up front; the float4 that straddles the end is assembled from scalar loads; elements past
             // the end add an exact +0 to bin 0 (not 0 x alpha, which is NaN for the alpha = inf of a bucket that holds an infinity)
-            const f4* g4 = (const f4*)(d.grad + e0) + lane;
+            const G4* g4 = (const G4*)((const G*)d.grad + e0) + lane;
             const uint32_t* i4 = (const uint32_t*)(d.idx + e0) + lane;
             const int64_t left = rem - 4 * lane;                        // elements from this lane's first float4 to the end
             f4 gv[4]; uint32_t pk[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int64_t lu = left - 256 * u;
-                const float* gs = (const float*)(g4 + 64 * u);
+                const G* gs = (const G*)(g4 + 64 * u);
                 const uint8_t* is = (const uint8_t*)(i4 + 64 * u);
                 float al[4];
                 alpha4(d, single, e0 + 256 * u + 4 * lane, lu, al);
                 f4 gq = {0.0f, 0.0f, 0.0f, 0.0f};
                 uint32_t pq = 0;
                 if (lu >= 4) {
-                    gq = ldg_nt(g4 + 64 * u);
+                    gq = load4(g4 + 64 * u, g8);
                     pq = ldg_nt(i4 + 64 * u);
                 } else {
-                    if (lu > 0) { gq.x = gs[0]; pq |= (uint32_t)is[0]; }
-                    if (lu > 1) { gq.y = gs[1]; pq |= (uint32_t)is[1] << 8; }
-                    if (lu > 2) { gq.z = gs[2]; pq |= (uint32_t)is[2] << 16; }
+                    if (lu > 0) { gq.x = widen(gs[0]); pq |= (uint32_t)is[0]; }
+                    if (lu > 1) { gq.y = widen(gs[1]); pq |= (uint32_t)is[1] << 8; }
+                    if (lu > 2) { gq.z = widen(gs[2]); pq |= (uint32_t)is[2] << 16; }
                 }
                 gv[u].x = lu > 0 ? gq.x * al[0] : 0.0f; gv[u].y = lu > 1 ? gq.y * al[1] : 0.0f;     // one fp32 multiply each, quant_functions.py:495
                 gv[u].z = lu > 2 ? gq.z * al[2] : 0.0f; gv[u].w = lu > 3 ? gq.w * al[3] : 0.0f;
@@ -358,14 +419,15 @@ __global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuant
             d = table[ti];
         }
         const int64_t e0 = (t - d.first_block) * kGradTile;
-        const bool aligned = ((((uintptr_t)d.grad) & 15) == 0) && ((((uintptr_t)d.idx) & 3) == 0);
+        const bool aligned = (!G32 || ((((uintptr_t)d.grad) & 15) == 0)) && ((((uintptr_t)d.idx) & 3) == 0);
+        const bool g8 = (((uintptr_t)d.grad) & 7) == 0;
         if (aligned) {                                                  // four (gradient float4, four indices, alpha) loads up front
-            const f4* g4 = (const f4*)(d.grad + e0) + lane;
+            const G4* g4 = (const G4*)((const G*)d.grad + e0) + lane;
             const uint32_t* i4 = (const uint32_t*)(d.idx + e0) + lane;
             f4 gv[4]; uint32_t pk[4]; float a[4][4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                gv[u] = ldg_nt(g4 + 64 * u);
+                gv[u] = load4(g4 + 64 * u, g8);
                 pk[u] = ldg_nt(i4 + 64 * u);
                 alpha4(d, d.n <= bucket, e0 + 256 * u + 4 * lane, 4, a[u]);                                 // n <= bucket: one alpha
             }
@@ -382,6 +444,19 @@ __global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuant
         }
     }
     flush(d, g);
+}
+
+template <int KR, int WPB, bool DIV>
+__global__ __launch_bounds__(64 * WPB) void k_multi_point_grad(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                               int64_t bucket, int row_shift, int k, float* part /* [rows][k] */) {
+    multi_point_grad<KR, WPB, DIV, float>(table, ntensors, bucket, row_shift, k, part);
+}
+
+// KIND: the grad_kind of the C ABI
+template <int KR, int WPB, bool DIV, int KIND>
+__global__ __launch_bounds__(64 * WPB) void k_multi_point_grad_in16(const QdDiffQuantDesc* __restrict__ table, int ntensors,
+                                                                    int64_t bucket, int row_shift, int k, float* part) {
+    multi_point_grad<KR, WPB, DIV, typename Grad16<KIND>::type>(table, ntensors, bucket, row_shift, k, part);
 }
 
 // backward stage 2: block (tensor, bin) folds the rows that tensor's waves wrote, front to back.  Up to 2048 + 1 rows per
@@ -414,12 +489,66 @@ __global__ __launch_bounds__(256) void k_multi_point_grad_final(const QdDiffQuan
     if (threadIdx.x == 0) grad_points[(int64_t)ti * k + j] = (float)((s_w[0] + s_w[1]) + (s_w[2] + s_w[3]));
 }
 
+// gradient sweep + fold of both backward entry points.  grad_kind 0: fp32 gradients
+int point_grad_launch(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k, int grad_kind,
+                      float* grad_points, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!table || ntensors <= 0 || total_blocks <= 0 || bucket < 0 || k < 1 || k > kMaxK || !grad_points)
+        return QD_ERR_INVALID_ARGUMENT;
+    // total_blocks is what qd_multi_dq_plan wrote: between 1 and 2048 + 1 partial rows per tensor
+    if (total_blocks < ntensors || total_blocks > (kGradWaves + 1) * (int64_t)ntensors) return QD_ERR_INVALID_ARGUMENT;
+    if (!workspace || (((uintptr_t)workspace) & 15) || workspace_bytes < (size_t)total_blocks * k * sizeof(float))
+        return QD_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    const bool div = (bucket & (bucket - 1)) != 0;                     // alpha[e / bucket] per element instead of alpha[e >> row_shift]
+    const int64_t kb = bucket == 0 ? INT64_MAX : bucket;               // no buckets: every tensor is "n <= bucket", one alpha
+    int row_shift = 0;
+    while (row_shift < 62 && ((int64_t)1 << row_shift) < kb) ++row_shift;
+    float* part = (float*)workspace;
+    // grid: the blocks of the sweep over the full tiles, 2048 waves in all (a wave beyond the last tile returns at once) + one
+    // wave per tensor for what is left after them
+    auto launch = [&](auto kernel, int wpb, size_t lds) {
+        const unsigned grid = (unsigned)(kGradWaves / wpb + (ntensors + wpb - 1) / wpb);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * wpb), lds, st, table, ntensors, kb, row_shift, k, part);
+    };
+    // KR, WPB: k <= 4 in registers; k <= 64 four waves per block; above, [k][64] columns: 64 KB at k = 256
+    const size_t lds4 = (size_t)k * 256 * sizeof(float), lds1 = (size_t)k * 64 * sizeof(float);
+#define QD_DQ_GRAD(KERNEL, ...)                                                                                            \
+    {                                                                                                                      \
+        if (k <= 4) {                                                                                                      \
+            if (div) launch(KERNEL<4, 4, true __VA_ARGS__>, 4, 0); else launch(KERNEL<4, 4, false __VA_ARGS__>, 4, 0);     \
+        } else if (k <= 64) {                                                                                              \
+            if (div) launch(KERNEL<0, 4, true __VA_ARGS__>, 4, lds4); else launch(KERNEL<0, 4, false __VA_ARGS__>, 4, lds4); \
+        } else {                                                                                                           \
+            if (div) launch(KERNEL<0, 1, true __VA_ARGS__>, 1, lds1); else launch(KERNEL<0, 1, false __VA_ARGS__>, 1, lds1); \
+        }                                                                                                                  \
+    }
+#define QD_COMMA ,
+    if (grad_kind == 0) QD_DQ_GRAD(k_multi_point_grad)
+    else if (grad_kind == QD_GRAD_F16) QD_DQ_GRAD(k_multi_point_grad_in16, QD_COMMA QD_GRAD_F16)
+    else QD_DQ_GRAD(k_multi_point_grad_in16, QD_COMMA QD_GRAD_BF16)
+#undef QD_COMMA
+#undef QD_DQ_GRAD
+    hipLaunchKernelGGL(k_multi_point_grad_final, dim3((unsigned)(ntensors * k)), dim3(256), 0, st, table, ntensors, k, part,
+                       grad_points);
+    return (int)hipGetLastError();
+}
+
+// what both forward entry points refuse
+inline bool nearest_args_ok(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles, int64_t bucket, const float* points,
+                            int k) {
+    return table && ntensors > 0 && total_tiles >= 0 && bucket >= 0 && points && k >= 1 && k <= kMaxK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t qd_multi_dq_plan(QdDiffQuantDesc* host_table, int ntensors, int64_t bucket, int64_t* total_blocks_out) {
     if (!host_table || ntensors <= 0 || bucket < 0 || !total_blocks_out) return -1;
+    // the only place that sees the pointers (the launches take a device table): an odd q or grad is wrong for every element
+    // type, the 16-bit ones of the _out16 / _in16 entry points included
+    for (int i = 0; i < ntensors; ++i)
+        if (host_table[i].n > 0 && ((((uintptr_t)host_table[i].q) | ((uintptr_t)host_table[i].grad)) & 1)) return -1;
     int64_t tiles = 0, gtiles = 0, rows = 0;
     for (int i = 0; i < ntensors; ++i) {
         const int64_t n = host_table[i].n;
@@ -439,8 +568,7 @@ int64_t qd_multi_dq_plan(QdDiffQuantDesc* host_table, int ntensors, int64_t buck
 
 int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles, int64_t bucket,
                          const float* points, int k, void* stream) {
-    if (!table || ntensors <= 0 || total_tiles < 0 || bucket < 0 || !points || k < 1 || k > kMaxK)
-        return QD_ERR_INVALID_ARGUMENT;
+    if (!nearest_args_ok(table, ntensors, total_tiles, bucket, points, k)) return QD_ERR_INVALID_ARGUMENT;
     if (total_tiles == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int blocks = grid_blocks(total_tiles, 4, kNoOwnCap);
@@ -452,39 +580,36 @@ int qd_multi_nearest_f32(const QdDiffQuantDesc* table, int ntensors, int64_t tot
     return (int)hipGetLastError();
 }
 
+int qd_multi_nearest_out16_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_tiles, int64_t bucket,
+                               const float* points, int k, int out_kind, void* stream) {
+    if (!nearest_args_ok(table, ntensors, total_tiles, bucket, points, k)) return QD_ERR_INVALID_ARGUMENT;
+    if (out_kind != QD_OUT_F16 && out_kind != QD_OUT_BF16) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = grid_blocks(total_tiles, 4, kNoOwnCap);
+#define QD_DQ_O16(OUT)                                                                                                      \
+    {                                                                                                                       \
+        if (bucket == 0) hipLaunchKernelGGL((k_multi_nearest_flat_o16<OUT>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, points, k); \
+        else if (bucket == 256) hipLaunchKernelGGL((k_multi_nearest_o16<256, OUT>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k); \
+        else if (bucket == 128) hipLaunchKernelGGL((k_multi_nearest_o16<128, OUT>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k); \
+        else if (bucket == 64) hipLaunchKernelGGL((k_multi_nearest_o16<64, OUT>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k); \
+        else hipLaunchKernelGGL((k_multi_nearest_o16<0, OUT>), dim3(blocks), dim3(256), 0, st, table, ntensors, total_tiles, bucket, points, k); \
+    }
+    if (out_kind == QD_OUT_F16) QD_DQ_O16(QD_OUT_F16)
+    else QD_DQ_O16(QD_OUT_BF16)
+#undef QD_DQ_O16
+    return (int)hipGetLastError();
+}
+
 int qd_multi_point_grad_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k,
                             float* grad_points, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!table || ntensors <= 0 || total_blocks <= 0 || bucket < 0 || k < 1 || k > kMaxK || !grad_points)
-        return QD_ERR_INVALID_ARGUMENT;
-    // total_blocks is what qd_multi_dq_plan wrote: between 1 and 2048 + 1 partial rows per tensor
-    if (total_blocks < ntensors || total_blocks > (kGradWaves + 1) * (int64_t)ntensors) return QD_ERR_INVALID_ARGUMENT;
-    if (!workspace || (((uintptr_t)workspace) & 15) || workspace_bytes < (size_t)total_blocks * k * sizeof(float))
-        return QD_ERR_WORKSPACE_TOO_SMALL;
-    hipStream_t st = (hipStream_t)stream;
-    const bool div = (bucket & (bucket - 1)) != 0;                     // alpha[e / bucket] per element instead of alpha[e >> row_shift]
-    const int64_t kb = bucket == 0 ? INT64_MAX : bucket;               // no buckets: every tensor is "n <= bucket", one alpha
-    int row_shift = 0;
-    while (row_shift < 62 && ((int64_t)1 << row_shift) < kb) ++row_shift;
-    float* part = (float*)workspace;
-    // grid: the blocks of the sweep over the full tiles, 2048 waves in all (a wave beyond the last tile returns at once) + one
-    // wave per tensor for what is left after them
-    auto launch = [&](auto kernel, int wpb, size_t lds) {
-        const unsigned grid = (unsigned)(kGradWaves / wpb + (ntensors + wpb - 1) / wpb);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * wpb), lds, st, table, ntensors, kb, row_shift, k, part);
-    };
-    if (k <= 4) {
-        if (div) launch(k_multi_point_grad<4, 4, true>, 4, 0);
-        else launch(k_multi_point_grad<4, 4, false>, 4, 0);
-    } else if (k <= 64) {
-        if (div) launch(k_multi_point_grad<0, 4, true>, 4, (size_t)k * 256 * sizeof(float));
-        else launch(k_multi_point_grad<0, 4, false>, 4, (size_t)k * 256 * sizeof(float));
-    } else {                                                           // [k][64] columns: 64 KB at k = 256
-        if (div) launch(k_multi_point_grad<0, 1, true>, 1, (size_t)k * 64 * sizeof(float));
-        else launch(k_multi_point_grad<0, 1, false>, 1, (size_t)k * 64 * sizeof(float));
-    }
-    hipLaunchKernelGGL(k_multi_point_grad_final, dim3((unsigned)(ntensors * k)), dim3(256), 0, st, table, ntensors, k, part,
-                       grad_points);
-    return (int)hipGetLastError();
+    return point_grad_launch(table, ntensors, total_blocks, bucket, k, 0, grad_points, workspace, workspace_bytes, stream);
+}
+
+int qd_multi_point_grad_in16_f32(const QdDiffQuantDesc* table, int ntensors, int64_t total_blocks, int64_t bucket, int k,
+                                 int grad_kind, float* grad_points, void* workspace, size_t workspace_bytes, void* stream) {
+    if (grad_kind != QD_GRAD_F16 && grad_kind != QD_GRAD_BF16) return QD_ERR_INVALID_ARGUMENT;
+    return point_grad_launch(table, ntensors, total_blocks, bucket, k, grad_kind, grad_points, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -16,18 +16,7 @@
 
 namespace {
 
-template <int OUT> struct Out16;
-template <> struct Out16<QD_OUT_F16> { typedef _Float16 type; };
-template <> struct Out16<QD_OUT_BF16> { typedef __bf16 type; };
-
-// four fp32 results as four 16-bit values: one 8-byte non-temporal store (the output is written once)
-template <typename O>
-__device__ __forceinline__ void store4_nt(const f4& r, O* dst) {
-    typedef O o4 __attribute__((ext_vector_type(4)));
-    o4 h;
-    h.x = (O)r.x; h.y = (O)r.y; h.z = (O)r.z; h.w = (O)r.w;
-    stg_nt(h, (o4*)dst);
-}
+// Out16<OUT>::type and store4_nt (four results, one 8-byte non-temporal store): qd_multi.h
 
 // bucket_lanes<MODE_QDQ, 16> (qd_transform.h) with a 16-bit store: a DPP row processes one arbitrary bucket [lo, hi) with scalar
 // accesses in two passes -- the ragged last bucket, short buckets, odd bucket sizes, pointers that the register path does not

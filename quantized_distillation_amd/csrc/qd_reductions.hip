@@ -674,38 +674,17 @@ __device__ __forceinline__ float ste_term(float g, float q, float x, float aq, f
 __device__ __forceinline__ unsigned ste_numerator_key(float x, float bq) { return __float_as_uint(fabsf(x - bq)) - 1u; }
 
 // The gradient's element type G: float (every fp32 entry point; the code below is then what it always was), or _Float16 /
-// __bf16 for qd_multi_ste_backward_in16_f32, which reads 16-bit gradients and widens them on load.  Widening is exact: bf16 is
-// the upper half of the fp32 pattern (an integer shift), fp16 goes through v_cvt_f32_f16 (subnormals kept, not flushed; the
-// sign of zero and +-inf kept; a NaN stays a NaN).  Everything after the load is the fp32 arithmetic, so a launch on 16-bit
+// __bf16 for qd_multi_ste_backward_in16_f32, which reads 16-bit gradients and widens them on load (Grad16<KIND>::type, widen,
+// load16x4_nt: qd_multi.h).  The widening is exact and everything after the load is the fp32 arithmetic, so a launch on 16-bit
 // gradients has the bits of the fp32 launch on a widened copy.
-template <int KIND> struct Grad16;                           // KIND: grad_kind of the C ABI, an int so that kernel names read alike
-template <> struct Grad16<QD_GRAD_F16> { typedef _Float16 type; };
-template <> struct Grad16<QD_GRAD_BF16> { typedef __bf16 type; };
-__device__ __forceinline__ float ste_widen(float g) { return g; }
-__device__ __forceinline__ float ste_widen(_Float16 g) { return (float)g; }
-__device__ __forceinline__ float ste_widen(__bf16 g) {
-    return __uint_as_float((unsigned)__builtin_bit_cast(unsigned short, g) << 16);
-}
 // this lane's four consecutive gradients of the register tile.  16-bit: one 8-byte load where g is 8-byte aligned (p is a
 // multiple of four elements past g: wave-uniform), element by element otherwise; the same lane -> element map either way.
-// (gfx950 under HSA runs with unaligned access allowed, and the compiler knows: it may fuse the four 2-byte loads again.)
 template <typename G>
 __device__ __forceinline__ f4 ste_load_g4(const G* p, bool g8) {
     if constexpr (std::is_same<G, float>::value) {
         return __builtin_nontemporal_load((const f4*)p);
     } else {
-        typedef unsigned short us4 __attribute__((ext_vector_type(4)));
-        us4 h;
-        if (g8) {
-            h = ldg_nt((const us4*)p);
-        } else {
-            const unsigned short* e = (const unsigned short*)p;
-            h.x = ldg_nt(e); h.y = ldg_nt(e + 1); h.z = ldg_nt(e + 2); h.w = ldg_nt(e + 3);
-        }
-        f4 r;
-        r.x = ste_widen(__builtin_bit_cast(G, (unsigned short)h.x)); r.y = ste_widen(__builtin_bit_cast(G, (unsigned short)h.y));
-        r.z = ste_widen(__builtin_bit_cast(G, (unsigned short)h.z)); r.w = ste_widen(__builtin_bit_cast(G, (unsigned short)h.w));
-        return r;
+        return load16x4_nt(p, g8);
     }
 }
 
@@ -869,7 +848,7 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const G* g, floa
                 float lev;
                 const float xv = x[i];
                 const float q = qdq(xv, a, b, sm1, 0.0f, lev);
-                s += ste_term<FAST>(ste_widen(g[i]), q, xv, aq, bq, yq);
+                s += ste_term<FAST>(widen(g[i]), q, xv, aq, bq, yq);
                 const float sv = tie_mode == QD_STE_TIE_REFERENCE ? q : xv;
                 const bool top = bad ? (sv != sv) : (sv == (tie_mode == QD_STE_TIE_REFERENCE ? qmx : mx));
                 const bool bot = bad ? (sv != sv) : (sv == (tie_mode == QD_STE_TIE_REFERENCE ? qmn : mn));
@@ -883,7 +862,7 @@ __device__ __forceinline__ void ste_wave_bucket(const float* x, const G* g, floa
         jmin = wave_min_ll(jmin);
         // pass 4: out = g, +S at jmax, -S at jmin (they cancel when the bucket is constant)
         for (int64_t i = lo + lane; i < hi; i += 64) {
-            float o = ste_widen(g[i]);
+            float o = widen(g[i]);
             if (jmax != jmin || bad) {                     // (a NaN bucket: (g + S) - S = NaN at the first NaN, as the reference)
                 if (i == jmax) o = o + s;
                 if (i == jmin) o = o - s;

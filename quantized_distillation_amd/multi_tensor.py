@@ -49,7 +49,7 @@ class _DeviceTable(object):
         one HIP device (self.device), each with as many elements as its counterpart in the first list and contiguous (the
         first list too unless first_contiguous=False: tensors that are only read through a copy).  dtypes: {what: dtype} for
         the lists that hold another type than fp32 (the 16-bit outputs of MultiTensorQuantizer, the 16-bit gradients of
-        MultiTensorSTE)."""
+        MultiTensorSTE, either of MultiTensorDiffQuant)."""
         lists = [list(ts) for ts in named.values()]
         if not lists[0]:
             raise ValueError('no tensors')
@@ -308,9 +308,35 @@ class MultiTensorDiffQuant(_DeviceTable):
     bucket_size: None (no buckets: one alpha / beta per tensor) or any positive int, as the per-tensor functions take them;
     num_points: 1 ... 256 (the index is a uint8).  Powers of two with at most 64 points are the tuned path; other bucket
     sizes and more points run the same launches through untuned instantiations.
+
+    A 16-bit student over fp32 masters: `outputs` may be all torch.float16 or all torch.bfloat16 (its p.data), and,
+    independently, `grads` may be all torch.float16 or all torch.bfloat16 (its p.grad).  The masters in `tensors`, the resident
+    u, alpha, beta, `points` and the gradient of the points stay fp32.  forward() then writes the IEEE round-to-nearest-even
+    conversion of what the fp32 launch writes -- outputs32[i].to(dtype), bit for bit, the same indices -- in the same single
+    launch (qd_multi_nearest_out16_f32); backward() returns what the fp32 launch gives on grads[i].float(), bit for bit,
+    whatever the alignment of the gradients (qd_multi_point_grad_in16_f32): no fp32 shadows, no torch._foreach_copy_ around
+    the sweeps.  `self.out_dtype` / `self.grad_dtype` keep the 16-bit types (None: fp32, which launches what it always
+    launched); rebind() takes tensors of the types given at construction.  `entry_point` names the C entry point of the last
+    forward() / backward().
     """
     _DESC = _lib.QdDiffQuantDesc
     _WATCH = ('outputs', 'grads')
+    _KINDS = {torch.float16: 1, torch.bfloat16: 2}              # QD_OUT_F16 = QD_GRAD_F16, QD_OUT_BF16 = QD_GRAD_BF16 (include/qd_hip.h)
+
+    @classmethod
+    def _one_dtype(cls, ts, what):
+        """The one dtype of the list `ts` as out_dtype / grad_dtype keep it: None for fp32, else one of the two 16-bit types.
+        TypeError for mixed lists and for any other dtype (what is no tensor at all is left to _adopt)."""
+        kinds = {t.dtype for t in ts if isinstance(t, torch.Tensor)}
+        if len(kinds) > 1:
+            raise TypeError('%s must all have one dtype, got %s' % (what, ', '.join(sorted(str(k) for k in kinds))))
+        have = kinds.pop() if kinds else torch.float32
+        if have != torch.float32 and have not in cls._KINDS:
+            raise TypeError('%s must be float32, float16 or bfloat16, got %s' % (what, have))
+        return None if have == torch.float32 else have
+
+    def _dtypes(self):
+        return {'outputs': self.out_dtype or torch.float32, 'grads': self.grad_dtype or torch.float32}
 
     def __init__(self, tensors, outputs, grads, num_points, bucket_size):
         from .quantization.quant_functions import ScalingFunction
@@ -324,7 +350,9 @@ class MultiTensorDiffQuant(_DeviceTable):
         # alive here for the lifetime of the object.  A caller that rebinds `p.grad` (zero_grad(set_to_none=True))
         # does not free them; backward() then reads the buffers given HERE, which is what the pointer check guards.
         # (the tensors themselves are read once, by scale_down, which copies: any layout)
-        tensors, self.outputs, self.grads = self._adopt(False, tensors=tensors, outputs=outputs, grads=grads)
+        tensors, outputs, grads = list(tensors), list(outputs), list(grads)
+        self.out_dtype, self.grad_dtype = self._one_dtype(outputs, 'outputs'), self._one_dtype(grads, 'grads')
+        tensors, self.outputs, self.grads = self._adopt(False, self._dtypes(), tensors=tensors, outputs=outputs, grads=grads)
         self.scalings, self.scaled, self.indices = [], [], []
         for t in tensors:
             sf = ScalingFunction('linear', False, False, bucket_size)
@@ -348,8 +376,9 @@ class MultiTensorDiffQuant(_DeviceTable):
 
     def rebind(self, outputs=None, grads=None):
         """Point the device table at new output / gradient buffers (e.g. after the caller re-allocated
-        its gradients) -- one small H2D copy."""
-        _, self.outputs, self.grads = self._adopt(scaled=self.scaled, outputs=self.outputs if outputs is None else outputs,
+        its gradients) -- one small H2D copy.  The new tensors have the dtypes given at construction (TypeError otherwise)."""
+        _, self.outputs, self.grads = self._adopt(True, self._dtypes(), scaled=self.scaled,
+                                                  outputs=self.outputs if outputs is None else outputs,
                                                   grads=self.grads if grads is None else grads)
         self._plan()
 
@@ -357,7 +386,11 @@ class MultiTensorDiffQuant(_DeviceTable):
         """points: [ntensors, k] fp32 device tensor, each row sorted.  Writes outputs[i] in place."""
         if points.shape != (self.n_tensors, self.k) or not points.is_contiguous():
             raise ValueError('points must be a contiguous [ntensors, k] tensor')
-        return self._launch(lambda: _lib.load().qd_multi_nearest_f32(
+        if self.out_dtype is not None:
+            return self._launch(lambda: self._entry('qd_multi_nearest_out16_f32')(
+                self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size or 0, points.data_ptr(), self.k,
+                self._KINDS[self.out_dtype], _lib.stream_ptr(self.device)), self.outputs)
+        return self._launch(lambda: self._entry('qd_multi_nearest_f32')(
             self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size or 0, points.data_ptr(), self.k,
             _lib.stream_ptr(self.device)), self.outputs)
 
@@ -365,7 +398,13 @@ class MultiTensorDiffQuant(_DeviceTable):
         """grad of the points from the gradient buffers given at construction: [ntensors, k]."""
         if out is None:
             out = torch.empty(self.n_tensors, self.k, dtype=torch.float32, device=self.device)
-        self._launch(lambda: _lib.load().qd_multi_point_grad_f32(
+        if self.grad_dtype is not None:
+            self._launch(lambda: self._entry('qd_multi_point_grad_in16_f32')(
+                self._table.data_ptr(), self.n_tensors, self._blocks, self.bucket_size or 0, self.k,
+                self._KINDS[self.grad_dtype], out.data_ptr(), self._scratch.data_ptr(), self._scratch.numel() * 4,
+                _lib.stream_ptr(self.device)))
+            return out
+        self._launch(lambda: self._entry('qd_multi_point_grad_f32')(
             self._table.data_ptr(), self.n_tensors, self._blocks, self.bucket_size or 0, self.k, out.data_ptr(),
             self._scratch.data_ptr(), self._scratch.numel() * 4, _lib.stream_ptr(self.device)))
         return out
