@@ -22,7 +22,7 @@ import torch
 
 import quantization
 from quantized_distillation_amd import _lib, ste
-from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer, MultiTensorSTE
+from quantized_distillation_amd.multi_tensor import MultiTensorQuantizer, MultiTensorSTE, per_channel_bucket_sizes
 
 from . import models
 from .flat import FlatLayout, GradSynchronizer, broadcast_from_rank0
@@ -48,7 +48,11 @@ class DistillTrainer(object):
         seed of the stochastic draws in device memory, so capture() records a step that rounds anew
         at every replay.  num_bits: one width for the whole model, or a sequence with one entry per parameter of the
         student (per-layer widths, e.g. 8 bits first and last, 4 or 2 in between); the entries of parameters that are not
-        quantized are ignored.  Both modes and every style take it."""
+        quantized are ignored.  Both modes and every style take it.  bucket_size: None, one size for the whole model,
+        'per_channel' (multi_tensor.per_channel_bucket_sizes of the student's parameters: one scale pair per output channel,
+        one bucket for a bias or a batch-norm vector) or a sequence with one entry per parameter of the student, taken like a
+        num_bits sequence: mode='multi' hands the quantized parameters' entries to MultiTensorQuantizer / MultiTensorSTE,
+        mode='per_tensor' hands entry i to the per-tensor calls."""
         style = 'none' if backprop_quantization_style is None else str(backprop_quantization_style).lower()
         if style not in STYLES:
             raise ValueError('The specified backprop_quantization_style not recognized')      # ref: :228-229
@@ -57,6 +61,14 @@ class DistillTrainer(object):
                                       ' Not hard to modify though')                           # ref: quant_functions.py:332-334
         if mode not in ('multi', 'per_tensor'):
             raise ValueError("mode must be 'multi' or 'per_tensor'")
+        if isinstance(bucket_size, (str, bytes)) and bucket_size != 'per_channel':
+            raise ValueError("bucket_size must be a positive integer, None, 'per_channel' or a sequence with one entry per parameter")
+        per_bucket = bucket_size is not None and not isinstance(bucket_size, numbers.Real)
+        per_channel = isinstance(bucket_size, (str, bytes))
+        if per_bucket and not per_channel:
+            bucket_size = list(bucket_size)
+            if any(isinstance(b, bool) or not isinstance(b, numbers.Integral) or b <= 0 for b in bucket_size):
+                raise ValueError('bucket_size entries must be positive integers, one per parameter')
         per_param = not isinstance(num_bits, numbers.Real)
         if per_param:
             num_bits = list(num_bits)
@@ -91,6 +103,13 @@ class DistillTrainer(object):
         if per_param and len(self.s) != n:
             raise ValueError('num_bits has %d entries for %d parameters: need one per parameter' % (len(self.s), n))
         self.s_of = self.s if per_param else [self.s] * n        # the level count of parameter i
+        if per_bucket:
+            if per_channel:
+                bucket_size = per_channel_bucket_sizes(params)
+            elif len(bucket_size) != n:
+                raise ValueError('bucket_size has %d entries for %d parameters: need one per parameter' % (len(bucket_size), n))
+            self.bucket_size = bucket_size
+        self.bucket_of = bucket_size if per_bucket else [bucket_size] * n        # the bucket size of parameter i
         self.quantized = [not (not quantize_first_and_last_layer and (i == 0 or i == n - 1)) for i in range(n)]
         layout = FlatLayout([p.shape for p in params])
         self.layout = layout
@@ -121,11 +140,12 @@ class DistillTrainer(object):
                 p.data = shadows[i] if self.quantized[i] else self.masters[i]
             qi = [i for i in range(n) if self.quantized[i]]
             s_q = [self.s_of[i] for i in qi] if per_param else self.s
-            self.mt = MultiTensorQuantizer([self.masters[i] for i in qi], s_q, bucket_size,
+            b_q = [self.bucket_of[i] for i in qi] if per_bucket else bucket_size
+            self.mt = MultiTensorQuantizer([self.masters[i] for i in qi], s_q, b_q,
                                            outputs=[shadows[i] for i in qi], stochastic_rounding=self.stochastic_rounding,
                                            max_element=max_element, seed_on_device=self.stochastic_rounding)
             if style == 'complicated':                           # K7 over all quantized masters, in place on the flat gradient
-                self.mt_ste = MultiTensorSTE([self.masters[i] for i in qi], [grads[i] for i in qi], s_q, bucket_size)
+                self.mt_ste = MultiTensorSTE([self.masters[i] for i in qi], [grads[i] for i in qi], s_q, b_q)
         else:
             for i, p in enumerate(params):
                 p.data = self.masters[i]
@@ -153,7 +173,7 @@ class DistillTrainer(object):
         else:                                                    # the reference's loop shape, :235-247
             for i, p in enumerate(self.params):
                 if self.quantized[i]:
-                    p.data = quantization.uniformQuantization(self.masters[i], self.s_of[i], bucket_size=self.bucket_size,
+                    p.data = quantization.uniformQuantization(self.masters[i], self.s_of[i], bucket_size=self.bucket_of[i],
                                                               stochastic_rounding=self.stochastic_rounding,
                                                               max_element=self.max_element)[0]
         self._quantized_step = True
@@ -185,7 +205,7 @@ class DistillTrainer(object):
             grads = self.layout.views(self.flat_grad)
             for i in range(len(self.params)):
                 if self.quantized[i]:
-                    ste.ste_bucket_backward(self.masters[i], grads[i], self.bucket_size, self.s_of[i], out=grads[i])
+                    ste.ste_bucket_backward(self.masters[i], grads[i], self.bucket_of[i], self.s_of[i], out=grads[i])
 
     def forward_backward(self, *batch):
         self.flat_grad.zero_()

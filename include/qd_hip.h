@@ -104,7 +104,9 @@ extern "C" {
  * count per tensor) are new symbols, likewise without a bump; so are qd_transform_plan and qd_set_grid_cap (host only), and
  * qd_multi_uniform_out16_f32 / qd_multi_uniform_global_out16_f32 (fp16 / bf16 outputs), and qd_multi_ste_in16_plan /
  * qd_multi_ste_backward_in16_f32 (fp16 / bf16 gradients), and qd_multi_nearest_out16_f32 / qd_multi_point_grad_in16_f32 (the
- * differentiable-quantization sweeps with fp16 / bf16 outputs and gradients; qd_multi_dq_plan now refuses an odd q or grad).
+ * differentiable-quantization sweeps with fp16 / bf16 outputs and gradients; qd_multi_dq_plan now refuses an odd q or grad),
+ * and qd_multi_buckets_plan / qd_multi_uniform_buckets_f32 / qd_multi_ste_buckets_plan / qd_multi_ste_backward_buckets_f32 (a
+ * bucket size per tensor).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -423,6 +425,38 @@ int qd_multi_ste_backward_levels_f32(const QdSteDesc* table, const int32_t* leve
 int qd_multi_ste_in16_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out);
 int qd_multi_ste_backward_in16_f32(const QdSteDesc* table, const int32_t* levels, int ntensors, int64_t total_tiles,
                                    int64_t bucket, int grad_kind, int tie_mode, void* stream);
+
+/* Multi-tensor K1 and K7 with a level count AND a bucket size PER TENSOR (per-channel scales: for a contiguous [out, ...] weight
+ * bucket_i = elements per output channel; what the per-tensor loop does when it calls uniformQuantization(t_i, s_i,
+ * bucket_size=b_i) and ste_bucket_backward(..., b_i, s_i)).  Device library only.  The descriptors are QdTensorDesc / QdSteDesc.
+ *   buckets: for the two plan calls a HOST array of ntensors int64 values, each > 0; for the two launches a DEVICE array of
+ *   ntensors int64 values, 8-byte aligned; entry i belongs to position i of the table, tensors without elements included.  The
+ *   kernels read it (one scalar load per tile) and never write it.  The device array MUST HOLD THE VALUES THE PLAN WAS MADE
+ *   WITH: the library cannot look into device memory without a synchronisation.  (An entry that disagrees gives wrong values
+ *   in, or leaves unwritten, tensors of that table and touches no other memory; an entry < 1 leaves its tensor unwritten.)
+ *   levels: the device int32 array of qd_multi_uniform_levels_f32, always (one level count for all: equal entries).
+ *   Tile rule of qd_multi_buckets_plan, with row = min(n, bucket) and nb = ceil(n / row): ceil(nb / 4) tiles for row <= 256 (a
+ *   DPP row per bucket; full 16-byte aligned rows of 64 / 128 / 256 are held in registers, other full aligned rows that are a
+ *   multiple of 4 are read as float4, the rest element by element), nb tiles for row > 256 (a wave per bucket, two passes).  A
+ *   row of more than 64 Ki elements runs on one wave: correct, not tuned -- whole-tensor scaling is qd_multi_uniform_global_*.
+ *   qd_multi_ste_buckets_plan counts as qd_multi_ste_plan does, tensor i under buckets[i].
+ *   Contract: tensor i of the table equals, bit for bit,
+ *       qd_uniform_f32(x_i, q_i, n_i, buckets[i], levels[i], NULL, NULL, NULL, NULL, clamp, max_element, stochastic, seed0 + i, ...)
+ *       qd_ste_bucket_backward_f32(x_i, g_i, out_i, n_i, buckets[i], levels[i], tie_mode, ...)
+ *   every bucket of the backward summed by the body and in the order that call uses.  q may alias x, out may alias g; nothing
+ *   is written outside [q_i, q_i + n_i) / [out_i, out_i + n_i).  A tensor without elements owns no tile and keeps its position
+ *   in levels, in buckets and in the seed rule.  The seed rule and the capture rule are those of qd_multi_uniform_opt_f32;
+ *   total_tiles == 0 returns 0 without a launch.  No workspace, no allocation, no synchronisation.
+ *   Errors (QD_ERR_INVALID_ARGUMENT, nothing written): levels or buckets NULL, levels not 4-byte or device buckets not 8-byte
+ *   aligned; in a plan call a buckets entry <= 0, ntensors <= 0, total_tiles_out NULL, n < 0 or a NULL pointer of a tensor that
+ *   has elements; everything qd_multi_uniform_levels_f32 / qd_multi_ste_backward_levels_f32 refuse. */
+int qd_multi_buckets_plan(QdTensorDesc* host_table, const int64_t* buckets, int ntensors, int64_t* total_tiles_out);
+int qd_multi_uniform_buckets_f32(const QdTensorDesc* table, const int32_t* levels, const int64_t* buckets, int ntensors,
+                                 int64_t total_tiles, int clamp, float max_element, int stochastic, uint64_t seed,
+                                 const uint64_t* seed_cell, void* stream);
+int qd_multi_ste_buckets_plan(QdSteDesc* host_table, const int64_t* buckets, int ntensors, int64_t* total_tiles_out);
+int qd_multi_ste_backward_buckets_f32(const QdSteDesc* table, const int32_t* levels, const int64_t* buckets, int ntensors,
+                                      int64_t total_tiles, int tie_mode, void* stream);
 
 /* ---- 'absmax' / 'absnorm' scaling (type_scaling of ScalingFunction, quant_functions.py:109-127,144-146).
  * PARITY UNPINNED: the reference code for these two types raises on every torch version, so these

@@ -128,6 +128,12 @@ SIGNATURES = {
     'qd_multi_ste_backward_levels_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_p]),
     'qd_multi_ste_in16_plan': (c_int, [ctypes.POINTER(QdSteDesc), c_int, i64, ctypes.POINTER(ctypes.c_int64)]),
     'qd_multi_ste_backward_in16_f32': (c_int, [c_p, c_p, c_int, i64, i64, c_int, c_int, c_p]),
+    'qd_multi_buckets_plan': (c_int, [ctypes.POINTER(QdTensorDesc), ctypes.POINTER(ctypes.c_int64), c_int,
+                                      ctypes.POINTER(ctypes.c_int64)]),
+    'qd_multi_uniform_buckets_f32': (c_int, [c_p, c_p, c_p, c_int, i64, c_int, c_float, c_int, u64, c_p, c_p]),
+    'qd_multi_ste_buckets_plan': (c_int, [ctypes.POINTER(QdSteDesc), ctypes.POINTER(ctypes.c_int64), c_int,
+                                          ctypes.POINTER(ctypes.c_int64)]),
+    'qd_multi_ste_backward_buckets_f32': (c_int, [c_p, c_p, c_p, c_int, i64, c_int, c_p]),
     'qd_uniform_abs_f32': (c_int, [c_f, c_f, i64, i64, c_int, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_scale_down_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_inv_scale_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_f, c_f, c_p]),

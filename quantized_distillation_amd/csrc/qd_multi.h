@@ -38,6 +38,25 @@ inline int64_t fill_prefix(Desc* host_table, int ntensors, Count items_of) {
     return total;
 }
 
+// ---- a bucket size per tensor (qd_multi_buckets_plan, k_multi_uniform_bk): the ONE statement of the tile rule ----
+// A tensor of n > 0 elements under its own bucket size has rows of row = min(n, bucket) elements, nb = ceil(n / row) of them.
+//   row <= 256: a tile is four buckets, a DPP row of the wave each -- ceil(nb / 4) tiles;
+//   row >  256: a tile is one bucket, the whole wave owns it      -- nb tiles.
+// The host plan counts with it and the kernel maps tile -> bucket with it, from the same two numbers.
+struct BucketTiles {
+    int64_t row, nb;     // elements per bucket row, number of buckets
+    int64_t tiles;       // wave iterations the tensor owns
+    bool wave;           // row > 256: one bucket per tile
+};
+__host__ __device__ __forceinline__ BucketTiles bucket_tiles(int64_t n, int64_t bucket) {
+    BucketTiles g;
+    g.row = n < bucket ? n : bucket;
+    g.nb = (n + g.row - 1) / g.row;
+    g.wave = g.row > 256;
+    g.tiles = g.wave ? g.nb : (g.nb + 3) / 4;
+    return g;
+}
+
 // ---- 16-bit elements of the launches that write fp16 / bf16 outputs or read fp16 / bf16 gradients ----
 // The kernels are instantiated on the out_kind / grad_kind of the C ABI (QD_OUT_F16 = QD_GRAD_F16 = 1, QD_OUT_BF16 =
 // QD_GRAD_BF16 = 2): an int, so that the kernel names read the same in every demangler.

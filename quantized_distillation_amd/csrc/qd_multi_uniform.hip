@@ -12,6 +12,10 @@
 //               at every replay, once the cell has been advanced on the stream).
 //   levels      qd_multi_uniform_levels_f32, qd_multi_uniform_global_levels_f32   k_multi_uniform_lv, k_mg_apply_lv: the forms with
 //               options again, with a level count per tensor from a device array beside the table ("8 bits first and last").
+//   buckets     qd_multi_buckets_plan, qd_multi_uniform_buckets_f32   k_multi_uniform_bk: the bucketed form with a level count
+//               AND a bucket size per tensor, both from device arrays (per-channel scales: bucket_i = elements per channel).
+//               The register body is chosen per tensor at run time; rows above 256 elements take a wave each.  A row of more
+//               than 64 Ki elements runs on one wave: functional, not tuned (whole-tensor scaling: the no-buckets form).
 #include "qd_transform.h"      // bucket_row16, KParams, Prep for k_multi_uniform; launch geometry
 #include "qd_multi.h"
 
@@ -524,6 +528,140 @@ __global__ __launch_bounds__(256) void k_mg_apply_lv(const QdTensorDesc* __restr
     }
 }
 
+// ---- a level count AND a bucket size per tensor (per-channel scales: bucket_i = elements per output channel) ----------------
+// One full, 16-byte aligned bucket row of 64 V elements held by the 16 lanes of a DPP row: the register body of
+// k_multi_uniform_lv, V a constant here and the row a run-time fact of the tensor.
+template <int V, int STOCH>
+__device__ __forceinline__ void bk_reg_row(const float* x, float* out, int64_t lo, int l, const Prep& pp, float sm1, bool use_tab,
+                                           float tab, uint64_t seed_t) {
+    const f4* src = (const f4*)(x + lo) + l;
+    f4 v[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = ldg_nt(src + j * 16);   // masters: read once
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = prep4(v[j], pp);        // the clamp comes before the bucket's min / max
+    float mn = pmin4(v[0]), mx = pmax4(v[0]);      // NaN-propagating
+#pragma unroll
+    for (int j = 1; j < V; ++j) { mn = pmin(mn, pmin4(v[j])); mx = pmax(mx, pmax4(v[j])); }
+    mn = row16_min(mn); mx = row16_max(mx);
+    float a, b, lev;
+    alpha_beta(mn, mx, a, b);
+    f4* dst = (f4*)(out + lo) + l;
+    const uint64_t blk0 = (uint64_t)(lo >> 2) + (uint64_t)l;      // Philox block of this lane's first float4
+    // rows of the wave that took this branch: all in the proven range -> bucket-invariant division (qd_common.h)
+    const bool fdiv = !__any(!fastdiv_ok(a));
+    auto body = [&](auto fast_c) {
+        constexpr bool FAST = decltype(fast_c)::value;
+        const float y = FAST ? 1.0f / a : 0.0f;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float rnd[4] = {0.f, 0.f, 0.f, 0.f};
+            if (STOCH) philox_uniform4(seed_t, blk0 + (uint64_t)(j * 16), rnd);
+            f4 r;
+            if (STOCH && use_tab) {                // <= 16 levels: a DPP row is active as a whole here
+                r.x = qdq_stochastic_tab<FAST>(v[j].x, a, b, sm1, 0.0f, rnd[0], lev, tab, y);
+                r.y = qdq_stochastic_tab<FAST>(v[j].y, a, b, sm1, 0.0f, rnd[1], lev, tab, y);
+                r.z = qdq_stochastic_tab<FAST>(v[j].z, a, b, sm1, 0.0f, rnd[2], lev, tab, y);
+                r.w = qdq_stochastic_tab<FAST>(v[j].w, a, b, sm1, 0.0f, rnd[3], lev, tab, y);
+            } else if (STOCH) {
+                r.x = qdq_stochastic<FAST>(v[j].x, a, b, sm1, 0.0f, rnd[0], lev, y);
+                r.y = qdq_stochastic<FAST>(v[j].y, a, b, sm1, 0.0f, rnd[1], lev, y);
+                r.z = qdq_stochastic<FAST>(v[j].z, a, b, sm1, 0.0f, rnd[2], lev, y);
+                r.w = qdq_stochastic<FAST>(v[j].w, a, b, sm1, 0.0f, rnd[3], lev, y);
+            } else if (use_tab) {
+                r.x = qdq_tab<FAST>(v[j].x, a, b, sm1, 0.0f, lev, tab, y);
+                r.y = qdq_tab<FAST>(v[j].y, a, b, sm1, 0.0f, lev, tab, y);
+                r.z = qdq_tab<FAST>(v[j].z, a, b, sm1, 0.0f, lev, tab, y);
+                r.w = qdq_tab<FAST>(v[j].w, a, b, sm1, 0.0f, lev, tab, y);
+            } else {
+                r.x = qdq<FAST>(v[j].x, a, b, sm1, 0.0f, lev, y);
+                r.y = qdq<FAST>(v[j].y, a, b, sm1, 0.0f, lev, y);
+                r.z = qdq<FAST>(v[j].z, a, b, sm1, 0.0f, lev, y);
+                r.w = qdq<FAST>(v[j].w, a, b, sm1, 0.0f, lev, y);
+            }
+            stg_nt(r, dst + j * 16);
+        }
+    };
+    if (fdiv) body(std::true_type{}); else body(std::false_type{});
+}
+
+// levels[ti] and buckets[ti] are read with the descriptor (wave-uniform: scalar loads); sm1, use_tab, tab and the tensor's
+// geometry (bucket_tiles, qd_multi.h: the rule qd_multi_buckets_plan counted with) are re-derived whenever the wave moves on to
+// another tensor.  Which body a bucket takes:
+//   row <= 256, a DPP row per bucket: a full row of a 16-byte aligned tensor takes the register body at row 64 / 128 / 256
+//     (a scalar branch on the row, the wave is uniform in it), bucket_lanes4<16> at any other multiple of 4; a ragged last row,
+//     a row that is no multiple of 4 and an unaligned tensor take bucket_row16;
+//   row > 256, the wave per bucket: bucket_lanes4<64> for a full row that is a multiple of 4 in an aligned tensor, else
+//     bucket_lanes<64>.  Two passes, the second served by L2.  A row of more than 64 Ki elements (a bucket size beyond the
+//     tensor included) still runs on that one wave: correct, not tuned -- whole-tensor scaling has the bucket_size=None launch.
+// Min / max do not depend on the order, the draws are indexed by element and the division is the bucket-invariant one only
+// where it is exact, so every body gives the bits of qd_uniform_f32 at (buckets[ti], levels[ti]).  A buckets entry < 1 (the
+// plan refuses one; the device array is the caller's) leaves its tensor unwritten and touches nothing else.
+template <int STOCH>
+__global__ __launch_bounds__(256) void k_multi_uniform_bk(const QdTensorDesc* __restrict__ table, const int32_t* __restrict__ levels,
+                                                          const int64_t* __restrict__ buckets, int ntensors, int64_t total_tiles,
+                                                          float me, uint64_t seed, const uint64_t* __restrict__ seed_cell) {
+    const int lane = threadIdx.x & 63;
+    const int sub = lane >> 4, l = lane & 15;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t seed0 = STOCH ? first_seed(seed, seed_cell) : 0;
+    Prep pp;
+    pp.mean = 0.0f;
+    pp.me = me;
+    int cur = -1;                                   // the tensor everything below belongs to
+    float sm1 = 1.0f, tab = 0.0f;
+    bool use_tab = false;
+    BucketTiles geo;
+    geo.row = 1; geo.nb = 0; geo.tiles = 0; geo.wave = false;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdTensorDesc d = table[ti];
+        if (d.n <= 0) continue;                     // (an empty tensor owns no tile)
+        if (ti != cur) {
+            cur = ti;
+            sm1 = (float)(levels[ti] - 1);
+            use_tab = sm1 <= 15.0f;
+            tab = (float)(lane & 15) / sm1;
+            const int64_t bucket = buckets[ti];
+            geo = bucket_tiles(d.n, bucket > 0 ? bucket : 1);
+            if (bucket <= 0) geo.nb = 0;            // no bucket of this tensor is reached
+        }
+        const uint64_t seed_t = seed0 + (uint64_t)ti;
+        KParams p;
+        p.x = d.x; p.out = d.q; p.n = d.n;
+        p.row = geo.row;
+        p.nb = geo.nb;
+        p.alpha = nullptr; p.beta = nullptr; p.mean = nullptr; p.me = me; p.sm1 = sm1; p.lev8 = nullptr;
+        p.idx = nullptr; p.idx_bytes = 0; p.pts = nullptr; p.k = 0; p.assign_mode = 0; p.prescaled = 0;
+        p.stochastic = STOCH; p.seed = seed_t; p.nvec = 0;
+        const int64_t local = t - d.first_tile;
+        const bool aligned = ((((uintptr_t)d.x) | ((uintptr_t)d.q)) & 15) == 0;     // rows that are a multiple of 4 then start aligned
+        const bool row4 = aligned && (p.row & 3) == 0;
+        if (geo.wave) {
+            const int64_t bkt = local;
+            if (bkt >= p.nb) continue;              // (a tile count that does not belong to this table reaches no bucket)
+            const int64_t lo = bkt * p.row;
+            const int64_t hi = lo + p.row < p.n ? lo + p.row : p.n;
+            if (row4 && hi - lo == p.row) bucket_lanes4<MODE_QDQ, 64>(p, nullptr, bkt, lo, lane, pp);
+            else bucket_lanes<MODE_QDQ, 64>(p, nullptr, bkt, lo, hi, lane, pp);
+        } else {
+            const int64_t bkt = local * 4 + sub;
+            if (bkt >= p.nb) continue;
+            const int64_t lo = bkt * p.row;
+            const int64_t hi = lo + p.row < p.n ? lo + p.row : p.n;
+            if (row4 && hi - lo == p.row) {
+                if (p.row == 256) bk_reg_row<4, STOCH>(p.x, p.out, lo, l, pp, sm1, use_tab, tab, seed_t);
+                else if (p.row == 128) bk_reg_row<2, STOCH>(p.x, p.out, lo, l, pp, sm1, use_tab, tab, seed_t);
+                else if (p.row == 64) bk_reg_row<1, STOCH>(p.x, p.out, lo, l, pp, sm1, use_tab, tab, seed_t);
+                else bucket_lanes4<MODE_QDQ, 16>(p, nullptr, bkt, lo, l, pp);
+            } else {
+                bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
+            }
+        }
+    }
+}
+
 // clamp != 0 needs a positive limit (not NaN); the limit the kernels see, +inf when the clamp is off
 inline bool clamp_limit(int clamp, float max_element, float& me) {
     me = clamp ? max_element : INFINITY;
@@ -668,6 +806,38 @@ int qd_multi_uniform_levels_f32(const QdTensorDesc* table, const int32_t* levels
     else if (bucket == 64) QD_MULTI_LV(64)
     else QD_MULTI_LV(0)
 #undef QD_MULTI_LV
+    return check_launch();
+}
+
+int qd_multi_buckets_plan(QdTensorDesc* host_table, const int64_t* buckets, int ntensors, int64_t* total_tiles_out) {
+    if (!host_table || !buckets || ntensors <= 0 || !total_tiles_out) return QD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < ntensors; ++i) {
+        const QdTensorDesc& d = host_table[i];
+        if (buckets[i] <= 0 || d.n < 0 || (d.n > 0 && (!d.x || !d.q))) return QD_ERR_INVALID_ARGUMENT;
+    }
+    *total_tiles_out = fill_prefix(host_table, ntensors, [host_table, buckets](const QdTensorDesc& d) -> int64_t {
+        return d.n > 0 ? bucket_tiles(d.n, buckets[&d - host_table]).tiles : 0;      // (the descriptor's position)
+    });
+    return 0;
+}
+
+int qd_multi_uniform_buckets_f32(const QdTensorDesc* table, const int32_t* levels, const int64_t* buckets, int ntensors,
+                                 int64_t total_tiles, int clamp, float max_element, int stochastic, uint64_t seed,
+                                 const uint64_t* seed_cell, void* stream) {
+    float me;
+    if (!table || !levels || (((uintptr_t)levels) & 3) || !buckets || (((uintptr_t)buckets) & 7) || ntensors <= 0 ||
+        total_tiles < 0 || !clamp_limit(clamp, max_element, me))
+        return QD_ERR_INVALID_ARGUMENT;
+    if (seed_cell && (((uintptr_t)seed_cell) & 7)) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int blocks = blocks_for(total_tiles, 4);
+    if (stochastic)
+        hipLaunchKernelGGL((k_multi_uniform_bk<1>), dim3(blocks), dim3(256), 0, st, table, levels, buckets, ntensors, total_tiles,
+                           me, seed, seed_cell);
+    else
+        hipLaunchKernelGGL((k_multi_uniform_bk<0>), dim3(blocks), dim3(256), 0, st, table, levels, buckets, ntensors, total_tiles,
+                           me, seed, seed_cell);
     return check_launch();
 }
 

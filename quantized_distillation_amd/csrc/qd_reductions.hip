@@ -8,6 +8,7 @@
 //   K7m qd_multi_ste_plan, qd_multi_ste_backward_f32  K7 of every parameter in one launch   conv_forward_model.py:253-266
 //       qd_multi_ste_backward_levels_f32              the same with a level count per tensor (k_multi_ste_lv)
 //       qd_multi_ste_in16_plan, qd_multi_ste_backward_in16_f32   the same reading fp16 / bf16 gradients (k_multi_ste_in16)
+//       qd_multi_ste_buckets_plan, qd_multi_ste_backward_buckets_f32   a level count and a bucket size per tensor (k_multi_ste_bk)
 // Its own translation unit so that hipcc builds it next to qd_kernels.hip / qd_nearest.hip / qd_scale.hip (parallel build).
 #include "qd_transform.h"      // shared helpers: workspace carving, launch geometry
 #include "qd_multi.h"          // owner_of, fill_prefix for K7m
@@ -1039,6 +1040,51 @@ __global__ __launch_bounds__(256) void k_multi_ste_lv(const QdSteDesc* __restric
     }
 }
 
+// k_multi_ste_lv with a bucket size per tensor as well (qd_multi_ste_backward_buckets_f32): buckets[ti] is read like levels[ti].
+// ste_cut<-1> -- the host callers' form, any row of QD_STE_SHAPES -- with the tensor's own bucket says which body sums each of
+// its buckets, as it told qd_multi_ste_buckets_plan and as it tells qd_ste_bucket_backward_f32; a scalar switch on the row then
+// calls that shape's ste_vec_tile.  A buckets entry < 1 (the plan refuses one) leaves its tensor unwritten.
+__global__ __launch_bounds__(256) void k_multi_ste_bk(const QdSteDesc* __restrict__ table, const int32_t* __restrict__ levels,
+                                                      const int64_t* __restrict__ buckets, int ntensors, int64_t total_tiles,
+                                                      int tie_mode) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = uniform_wave_index();      // scalar: owner_of runs on s_load
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    int cur = -1;                                   // the tensor sm1 / use_tab / tab / bucket below belong to
+    float sm1 = 1.0f, tab = 0.0f;
+    bool use_tab = false;
+    int64_t bucket = 0;
+    for (int64_t t = wave; t < total_tiles; t += nwaves) {
+        const int ti = owner_of(table, ntensors, t);
+        const QdSteDesc d = table[ti];                                  // (an empty tensor owns no tile)
+        if (d.n <= 0) continue;
+        if (ti != cur) {
+            cur = ti;
+            sm1 = (float)(levels[ti] - 1);
+            use_tab = sm1 <= 15.0f;
+            tab = (float)(lane & 15) / sm1;
+            bucket = buckets[ti];
+        }
+        if (bucket <= 0) continue;
+        const int64_t local = t - d.first_tile;
+        const SteCut c = ste_cut<-1>(d.x, d.g, d.out, d.n, bucket);
+        if (local < c.vtiles) {
+            switch (c.row) {
+#define QD_STE_BK_CASE(ROW, LPB, V)                                                                                      \
+            case ROW:                                                                                                    \
+                ste_vec_tile<LPB, V>(d.x, d.g, d.out, c.nfull, local, lane / LPB, lane % LPB, sm1, tie_mode, use_tab, tab); \
+                break;
+            QD_STE_SHAPES(QD_STE_BK_CASE)
+#undef QD_STE_BK_CASE
+            default: break;
+            }
+        } else {
+            const int64_t bkt = c.nfull + (local - c.vtiles);   // (a tile count that does not belong to this table reaches no bucket)
+            if (local >= 0 && bkt * c.row < d.n) ste_wave_bucket(d.x, d.g, d.out, d.n, c.row, bkt, lane, sm1, tie_mode);
+        }
+    }
+}
+
 // k_multi_ste_lv reading 16-bit gradients (qd_multi_ste_backward_in16_f32): d.g addresses n fp16 / bf16 elements, x and out stay
 // fp32, out never aliases g.  The same tile loop and the same two bodies, instantiated for the gradient's type.  The cut is made
 // from n, bucket, x and out alone (no g goes to ste_cut) -- g's alignment must not decide which body sums a bucket -- which is
@@ -1326,6 +1372,31 @@ int qd_multi_ste_backward_levels_f32(const QdSteDesc* table, const int32_t* leve
     return check_launch();
 }
 
+int qd_multi_ste_buckets_plan(QdSteDesc* host_table, const int64_t* buckets, int ntensors, int64_t* total_tiles_out) {
+    if (!host_table || !buckets || ntensors <= 0 || !total_tiles_out) return QD_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < ntensors; ++i) {
+        const QdSteDesc& d = host_table[i];
+        if (buckets[i] <= 0 || d.n < 0 || (d.n > 0 && (!d.x || !d.g || !d.out))) return QD_ERR_INVALID_ARGUMENT;
+    }
+    *total_tiles_out = fill_prefix(host_table, ntensors, [host_table, buckets](const QdSteDesc& d) -> int64_t {
+        if (d.n <= 0) return 0;
+        const SteCut c = ste_cut(d.x, d.g, d.out, d.n, buckets[&d - host_table]);       // (the descriptor's position)
+        return c.vtiles + (c.nb - c.nfull);
+    });
+    return 0;
+}
+
+int qd_multi_ste_backward_buckets_f32(const QdSteDesc* table, const int32_t* levels, const int64_t* buckets, int ntensors,
+                                      int64_t total_tiles, int tie_mode, void* stream) {
+    if (!table || !levels || (((uintptr_t)levels) & 3) || !buckets || (((uintptr_t)buckets) & 7) || ntensors <= 0 ||
+        total_tiles < 0)
+        return QD_ERR_INVALID_ARGUMENT;
+    if (tie_mode != QD_STE_TIE_REFERENCE && tie_mode != QD_STE_TIE_TRUE_ARG) return QD_ERR_INVALID_ARGUMENT;
+    if (total_tiles == 0) return 0;
+    hipLaunchKernelGGL(k_multi_ste_bk, dim3(blocks_for(total_tiles, 4)), dim3(256), 0, (hipStream_t)stream, table, levels,
+                       buckets, ntensors, total_tiles, tie_mode);
+    return check_launch();
+}
 
 int qd_multi_ste_in16_plan(QdSteDesc* host_table, int ntensors, int64_t bucket, int64_t* total_tiles_out) {
     if (!host_table || ntensors <= 0 || bucket <= 0 || !total_tiles_out) return QD_ERR_INVALID_ARGUMENT;

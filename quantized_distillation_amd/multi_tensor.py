@@ -36,6 +36,45 @@ def _level_counts(s, tensors):
     return counts, tensors
 
 
+def _is_bucket_list(bucket_size):
+    """bucket_size of the uniform one-launch classes is given per tensor: anything but None and a single number."""
+    return bucket_size is not None and not isinstance(bucket_size, numbers.Real)
+
+
+def _bucket_sizes(bucket_size, tensors):
+    """A bucket_size given per tensor: a sequence of positive integers, one per tensor.  Returns (the tuple `self.bucket_size`
+    keeps, the list of tensors); as in _level_counts only the list's length is looked at, no tensor is."""
+    if isinstance(bucket_size, (str, bytes)) or not hasattr(bucket_size, '__iter__'):
+        raise ValueError('bucket_size must be a positive integer, None, or a sequence of positive integers with one entry per '
+                         'tensor')
+    sizes = []
+    for v in bucket_size:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 < v < 2 ** 63:
+            raise ValueError('bucket_size entries must be positive integers, got %r' % (v,))
+        sizes.append(int(v))
+    tensors = list(tensors)
+    if len(sizes) != len(tensors):
+        raise ValueError('bucket_size has %d entries for %d tensors: need one per tensor' % (len(sizes), len(tensors)))
+    return tuple(sizes), tensors
+
+
+def per_channel_bucket_sizes(tensors):
+    """The bucket_size list that gives every tensor one (alpha, beta) pair per output channel: the elements of t[0] for a
+    tensor of two or more dimensions (a contiguous [out, ...] weight: buckets are flat runs, so a run of that length is a
+    channel), and the whole tensor -- one bucket -- for a bias, a batch-norm vector or a scalar.  Never below 1, so that a
+    tensor without elements keeps a valid entry.  Pure Python: no device, no tensor data is looked at."""
+    sizes = []
+    for t in tensors:
+        if t.dim() >= 2:
+            per = 1
+            for extent in t.shape[1:]:
+                per *= int(extent)
+            sizes.append(max(per, 1))
+        else:
+            sizes.append(max(int(t.numel()), 1))
+    return sizes
+
+
 class _DeviceTable(object):
     """What the one-launch classes share: the argument check, the descriptor table on the device, and the launch on a table
     that is current.  A subclass names its descriptor type, says which tensors go into which field (_columns), calls the
@@ -120,6 +159,21 @@ class _DeviceTable(object):
         self._s = None if mixed else (s[0] if isinstance(s, tuple) else s)
         self._levels = torch.tensor(s, dtype=torch.int32, device=self.device) if mixed else None
 
+    def _plan_buckets(self, plan, host, n):
+        """_plan_table of an object whose bucket_size is a tuple, one entry per tensor: `plan` (qd_multi_buckets_plan /
+        qd_multi_ste_buckets_plan) counts tensor i under entry i, and self._buckets becomes the int64 device array the launch
+        reads -- built here, next to the table, from the values the plan was made with; returns the tile count."""
+        sizes = (ctypes.c_int64 * n)(*self.bucket_size)
+        tiles = ctypes.c_int64(0)
+        _lib.check(plan(host, sizes, n, ctypes.byref(tiles)))
+        self._buckets = torch.tensor(self.bucket_size, dtype=torch.int64, device=self.device)
+        return int(tiles.value)
+
+    def _own_levels(self, n):
+        """The entry points that take a levels array take it always: one for equal entries too."""
+        if self._levels is None:
+            self._levels = torch.full((n,), self._s, dtype=torch.int32, device=self.device)
+
 
 class MultiTensorQuantizer(_DeviceTable):
     """uniformQuantization(t, s, bucket_size=bucket_size, stochastic_rounding=..., max_element=...)[0] of every tensor, written
@@ -140,6 +194,13 @@ class MultiTensorQuantizer(_DeviceTable):
     as an int32 device array and every option combination launches qd_multi_uniform_levels_f32 /
     qd_multi_uniform_global_levels_f32; a scalar, or a sequence whose entries are all equal, launches what it always
     launched.  `entry_point` names the C entry point the last quantize() went through.
+
+    bucket_size: None, one positive int for every tensor, or a sequence of positive ints with one entry per tensor (tensor i
+    equals uniformQuantization(t_i, s_i, bucket_size=bucket_size[i], ...); per_channel_bucket_sizes(tensors) gives the list
+    for one scale pair per output channel); `self.bucket_size` keeps None, the int or a tuple.  A sequence -- equal entries
+    included -- always plans with qd_multi_buckets_plan and launches qd_multi_uniform_buckets_f32, whatever the options and
+    the form of s; the int64 device array it reads is the object's own and is rebuilt with the table.  Every option above
+    works as with one bucket size.  Not with fp16 / bf16 outputs: NotImplementedError.
 
     out_dtype: None (fp32 outputs: everything above, unchanged), torch.float16 or torch.bfloat16 -- fp32 masters quantized
     straight into a 16-bit model.  `outputs` may then be a list of tensors that are all fp16 or all bf16 (their dtype is
@@ -175,9 +236,12 @@ class MultiTensorQuantizer(_DeviceTable):
 
     def __init__(self, tensors, s, bucket_size, outputs=None, stochastic_rounding=False, max_element=False,
                  subtract_mean=False, seed_on_device=False, out_dtype=None):
-        if bucket_size is not None and (not isinstance(bucket_size, int) or bucket_size <= 0):
+        per_tensor = _is_bucket_list(bucket_size)
+        if not per_tensor and bucket_size is not None and (not isinstance(bucket_size, int) or bucket_size <= 0):
             raise ValueError('bucket_size must be a positive integer or None')
         s, tensors = _level_counts(s, tensors)
+        if per_tensor:
+            bucket_size, tensors = _bucket_sizes(bucket_size, tensors)
         if max_element is not False and (max_element is True or not isinstance(max_element, numbers.Number)):
             raise ValueError('maxElementAllowed must be a number')                  # as ScalingFunction, ref: :31-33
         if subtract_mean:
@@ -193,6 +257,10 @@ class MultiTensorQuantizer(_DeviceTable):
         self.seed_cell = None
         outputs = None if outputs is None else list(outputs)
         self.out_dtype = self._output_dtype(outputs, out_dtype)
+        self._buckets = None                       # the int64 device array of a per-tensor bucket_size (_plan_buckets)
+        if per_tensor and self.out_dtype is not None:
+            raise NotImplementedError('MultiTensorQuantizer: a bucket_size per tensor together with fp16 / bf16 outputs is not '
+                                      'implemented: give one bucket_size, or fp32 outputs')
         if outputs is None:
             (self.inputs,) = self._adopt(tensors=tensors)
             self.outputs = [torch.empty_like(t, dtype=self.out_dtype) for t in self.inputs]
@@ -202,6 +270,8 @@ class MultiTensorQuantizer(_DeviceTable):
         self._bind_levels(s)
         if self.out_dtype is not None and self._levels is None:     # the 16-bit entry points take the array, always
             self._levels = torch.full((len(self.inputs),), self._s, dtype=torch.int32, device=self.device)
+        if per_tensor:                                              # ... and so does the per-tensor-bucket entry point
+            self._own_levels(len(self.inputs))
         self._plan()
         if self.seed_on_device:
             self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -215,6 +285,8 @@ class MultiTensorQuantizer(_DeviceTable):
             tiles = int(_lib.load().qd_multi_global_plan(host, n))
             self.alpha_beta = torch.empty(n, 2, dtype=torch.float32, device=self.device)     # per-tensor (alpha, beta)
             self._scratch = torch.empty(max(4, 2 * tiles), dtype=torch.float32, device=self.device)
+        elif isinstance(self.bucket_size, tuple):
+            tiles = self._plan_buckets(_lib.load().qd_multi_buckets_plan, host, n)
         else:
             tiles = int(_lib.load().qd_multi_plan(host, n, self.bucket_size))
         if tiles < 0:
@@ -241,6 +313,10 @@ class MultiTensorQuantizer(_DeviceTable):
                     self._scratch.numel() * 4, _lib.stream_ptr(self.device))
             return self._entry('qd_multi_uniform_out16_f32')(
                 self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, kind, clamp, me,
+                int(self.stochastic_rounding), seed, cell, _lib.stream_ptr(self.device))
+        if self._buckets is not None:              # a bucket size per tensor: one entry point for every option and every s
+            return self._entry('qd_multi_uniform_buckets_f32')(
+                self._table.data_ptr(), self._levels.data_ptr(), self._buckets.data_ptr(), self.n_tensors, self._tiles, clamp, me,
                 int(self.stochastic_rounding), seed, cell, _lib.stream_ptr(self.device))
         if self._levels is not None:               # a level count per tensor: the one pair of entry points for every option
             if self.bucket_size is None:
@@ -340,6 +416,9 @@ class MultiTensorDiffQuant(_DeviceTable):
 
     def __init__(self, tensors, outputs, grads, num_points, bucket_size):
         from .quantization.quant_functions import ScalingFunction
+        if _is_bucket_list(bucket_size) and not isinstance(bucket_size, (str, bytes)) and hasattr(bucket_size, '__iter__'):
+            raise NotImplementedError('MultiTensorDiffQuant with a bucket_size per tensor is not implemented: give one '
+                                      'bucket_size (MultiTensorQuantizer and MultiTensorSTE take a sequence)')
         if bucket_size is not None and (type(bucket_size) is not int or bucket_size <= 0):      # as ScalingFunction (bool refused)
             raise ValueError('Bucket size must be an integer and strictly positive. '
                              'Pass None if you want to avoid using buckets')
@@ -422,6 +501,9 @@ class MultiTensorSTE(_DeviceTable):
     s: one level count, or a sequence with one entry per tensor (s[i] in the call above), as MultiTensorQuantizer takes it:
     unequal entries launch qd_multi_ste_backward_levels_f32, anything else the entry point above (`entry_point` names the one
     the last backward() took).
+    bucket_size: one positive int, or a sequence of positive ints with one entry per tensor (bucket_size[i] in the call above),
+    as MultiTensorQuantizer takes it: a sequence always plans with qd_multi_ste_buckets_plan and launches
+    qd_multi_ste_backward_buckets_f32 (fp32 gradients only: NotImplementedError with 16-bit ones).
 
     grads may instead be all torch.float16 or all torch.bfloat16 -- the p.grad of a 16-bit student over fp32 masters.
     `weights` stay fp32 and `outs` is a list of fp32 tensors (outs=None: allocated, one per gradient; there is no in-place form,
@@ -450,15 +532,22 @@ class MultiTensorSTE(_DeviceTable):
         if bucket_size is None:                                                         # ref: quant_functions.py:332-334
             raise NotImplementedError('Right now the code does not work with bucket_size None.'
                                       ' Not hard to modify though')
-        if isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0:
+        per_tensor = _is_bucket_list(bucket_size)
+        if not per_tensor and (isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0):
             raise ValueError('bucket_size must be a positive integer')
         s, weights = _level_counts(s, weights)
+        if per_tensor:
+            bucket_size, weights = _bucket_sizes(bucket_size, weights)
         if tie_mode not in ('reference', 'true_arg'):
             raise ValueError("tie_mode must be 'reference' or 'true_arg'")
         self.bucket_size = bucket_size
         self.tie_mode = 0 if tie_mode == 'reference' else 1
         grads = list(grads)
         self.grad_dtype = self._gradient_dtype(grads)
+        self._buckets = None                       # the int64 device array of a per-tensor bucket_size (_plan_buckets)
+        if per_tensor and self.grad_dtype is not None:
+            raise NotImplementedError('MultiTensorSTE: a bucket_size per tensor together with fp16 / bf16 grads is not '
+                                      'implemented: give one bucket_size, or fp32 gradients')
         # OWNING references: the device table holds raw pointers into these tensors
         if self.grad_dtype is not None:
             if outs is None:
@@ -475,12 +564,16 @@ class MultiTensorSTE(_DeviceTable):
         self._bind_levels(s)
         if self.grad_dtype is not None and self._levels is None:    # the 16-bit entry point takes the array, always
             self._levels = torch.full((len(self.weights),), self._s, dtype=torch.int32, device=self.device)
+        if per_tensor:                                              # ... and so does the per-tensor-bucket entry point
+            self._own_levels(len(self.weights))
         self._plan()
 
     def _columns(self):
         return ('x', self.weights), ('g', self.grads), ('out', self.outs)
 
     def _plan_table(self, host, n):
+        if isinstance(self.bucket_size, tuple):
+            return self._plan_buckets(_lib.load().qd_multi_ste_buckets_plan, host, n)
         tiles = ctypes.c_int64(0)
         plan = _lib.load().qd_multi_ste_plan if self.grad_dtype is None else _lib.load().qd_multi_ste_in16_plan
         _lib.check(plan(host, n, self.bucket_size, ctypes.byref(tiles)))
@@ -492,6 +585,10 @@ class MultiTensorSTE(_DeviceTable):
             return self._launch(lambda: self._entry('qd_multi_ste_backward_in16_f32')(
                 self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size,
                 self._GRAD_KINDS[self.grad_dtype], self.tie_mode, _lib.stream_ptr(self.device)), self.outs, check_pointers)
+        if self._buckets is not None:
+            return self._launch(lambda: self._entry('qd_multi_ste_backward_buckets_f32')(
+                self._table.data_ptr(), self._levels.data_ptr(), self._buckets.data_ptr(), self.n_tensors, self._tiles,
+                self.tie_mode, _lib.stream_ptr(self.device)), self.outs, check_pointers)
         if self._levels is not None:
             return self._launch(lambda: self._entry('qd_multi_ste_backward_levels_f32')(
                 self._table.data_ptr(), self._levels.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self.tie_mode,
