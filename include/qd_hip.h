@@ -106,7 +106,8 @@ extern "C" {
  * qd_multi_ste_backward_in16_f32 (fp16 / bf16 gradients), and qd_multi_nearest_out16_f32 / qd_multi_point_grad_in16_f32 (the
  * differentiable-quantization sweeps with fp16 / bf16 outputs and gradients; qd_multi_dq_plan now refuses an odd q or grad),
  * and qd_multi_buckets_plan / qd_multi_uniform_buckets_f32 / qd_multi_ste_buckets_plan / qd_multi_ste_backward_buckets_f32 (a
- * bucket size per tensor).
+ * bucket size per tensor), and qd_multi_symbols_plan / qd_multi_uniform_symbols_u8 (QdSymbolDesc: the symbols of a whole model in
+ * one launch).
  * The Python binding and _qd_glue.so compare the version THEY were built for with the library's. */
 #define QD_ABI_VERSION 3
 int qd_abi_version(void);
@@ -457,6 +458,42 @@ int qd_multi_uniform_buckets_f32(const QdTensorDesc* table, const int32_t* level
 int qd_multi_ste_buckets_plan(QdSteDesc* host_table, const int64_t* buckets, int ntensors, int64_t* total_tiles_out);
 int qd_multi_ste_backward_buckets_f32(const QdSteDesc* table, const int32_t* levels, const int64_t* buckets, int ntensors,
                                       int64_t total_tiles, int tie_mode, void* stream);
+
+/* The SYMBOLS of a whole model in one launch: what a compressed checkpoint stores of a uniformly quantized tensor -- the uint8
+ * level index of every weight and the (alpha, beta) of every bucket -- for every tensor of a table, each under its own level
+ * count and its own bucket size, without the fp32 result (4 B read + 1 B written per element; the per-tensor loop over
+ * qd_uniform_f32 with its level output moves 9 B and launches once per tensor).  Device library only.
+ *   buckets, levels: as for qd_multi_uniform_buckets_f32 -- buckets a HOST array for the plan and an 8-byte aligned DEVICE array
+ *   holding the same values for the launch, levels a DEVICE int32 array, entry i for position i of the table; neither is written.
+ *   qd_multi_symbols_plan counts tiles by the tile rule of qd_multi_buckets_plan and fills first_tile and first_bucket, the
+ *   running sum of nb = ceil(n / min(n, bucket)); *total_buckets_out is the length alpha and beta need.
+ *   Contract: tensor i of the table equals, bit for bit, the level_idx, alpha and beta of
+ *       qd_uniform_f32(x_i, <scratch>, n_i, buckets[i], levels[i], alpha + first_bucket_i, beta + first_bucket_i, sym_i,
+ *                      NULL, 0, 0, 0, 0, ...)
+ *   deterministic rounding, no clamp, no mean: level = rint(((v - beta) / alpha) * (levels - 1)), each operation rounded to
+ *   fp32, stored as (uint8_t)(int)level -- a bucket that holds a NaN or an infinity gets symbol 0 and that call's alpha / beta.
+ *   Neither the alignment of x_i (any multiple of 4) nor that of sym_i (any) changes a bit.  Nothing is written outside
+ *   [sym_i, sym_i + n_i), alpha[first_bucket_i .. + nb_i) and beta[first_bucket_i .. + nb_i); x is never written.  A tensor
+ *   without elements owns no tile and no bucket and keeps its position in levels and buckets.  A levels entry outside 2 .. 256
+ *   or a buckets entry that disagrees with the plan may give wrong values in that tensor's own outputs: symbol addresses are
+ *   bounded by n_i, alpha / beta indices by the next descriptor's first_bucket (for the table's last tensor by
+ *   ceil(n / min(n, buckets[i])): alpha and beta hold the plan's total_buckets entries under the values the plan was made with);
+ *   a buckets entry < 1 leaves its tensor unwritten.  total_tiles == 0 returns 0 without a launch.  No workspace, no
+ *   allocation, no synchronisation: the launch can be captured into a graph.
+ *   Errors (QD_ERR_INVALID_ARGUMENT, nothing written): table, levels, buckets, alpha or beta NULL; levels, alpha or beta not
+ *   4-byte, device buckets not 8-byte aligned; ntensors <= 0, total_tiles < 0; in the plan a NULL output, a buckets entry <= 0,
+ *   n < 0 or a NULL pointer of a tensor that has elements. */
+typedef struct QdSymbolDesc {
+    const float* x;        /* n fp32 weights, 4-byte aligned; never written            */
+    uint8_t* sym;          /* n level indices, any alignment; must not overlap x       */
+    int64_t n;
+    int64_t first_tile;    /* filled by the plan                                       */
+    int64_t first_bucket;  /* filled by the plan: index of the tensor's first bucket   */
+} QdSymbolDesc;
+int qd_multi_symbols_plan(QdSymbolDesc* host_table, const int64_t* buckets, int ntensors, int64_t* total_tiles_out,
+                          int64_t* total_buckets_out);
+int qd_multi_uniform_symbols_u8(const QdSymbolDesc* table, const int32_t* levels, const int64_t* buckets, int ntensors,
+                                int64_t total_tiles, float* alpha, float* beta, void* stream);
 
 /* ---- 'absmax' / 'absnorm' scaling (type_scaling of ScalingFunction, quant_functions.py:109-127,144-146).
  * PARITY UNPINNED: the reference code for these two types raises on every torch version, so these

@@ -55,6 +55,12 @@ class QdDiffQuantDesc(ctypes.Structure):
                 ('first_tile', ctypes.c_int64), ('first_block', ctypes.c_int64), ('first_row', ctypes.c_int64)]
 
 
+class QdSymbolDesc(ctypes.Structure):
+    """Mirror of `struct QdSymbolDesc` in include/qd_hip.h."""
+    _fields_ = [('x', ctypes.c_void_p), ('sym', ctypes.c_void_p), ('n', ctypes.c_int64), ('first_tile', ctypes.c_int64),
+                ('first_bucket', ctypes.c_int64)]
+
+
 class QdHufTensor(ctypes.Structure):
     """Mirror of `struct QdHufTensor` in include/qd_hip.h."""
     _fields_ = [('sym', ctypes.c_void_p), ('y', ctypes.c_void_p), ('n', ctypes.c_int64), ('first_chunk', ctypes.c_int64),
@@ -134,6 +140,9 @@ SIGNATURES = {
     'qd_multi_ste_buckets_plan': (c_int, [ctypes.POINTER(QdSteDesc), ctypes.POINTER(ctypes.c_int64), c_int,
                                           ctypes.POINTER(ctypes.c_int64)]),
     'qd_multi_ste_backward_buckets_f32': (c_int, [c_p, c_p, c_p, c_int, i64, c_int, c_p]),
+    'qd_multi_symbols_plan': (c_int, [ctypes.POINTER(QdSymbolDesc), ctypes.POINTER(ctypes.c_int64), c_int,
+                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    'qd_multi_uniform_symbols_u8': (c_int, [c_p, c_p, c_p, c_int, i64, c_f, c_f, c_p]),
     'qd_uniform_abs_f32': (c_int, [c_f, c_f, i64, i64, c_int, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_scale_down_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_int, c_f, c_f, c_int, c_float, c_p, c_size, c_p]),
     'qd_inv_scale_abs_f32': (c_int, [c_f, c_f, c_f, i64, i64, c_f, c_f, c_p]),

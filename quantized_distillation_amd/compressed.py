@@ -17,6 +17,7 @@ qd_huffman_encode / qd_huffman_decode_f32 (csrc/qd_huffman.hip, csrc/host/qd_hos
 """
 import collections
 import ctypes
+import fractions
 import math
 import numbers
 import struct
@@ -27,6 +28,7 @@ import torch
 
 from . import _lib
 from .codec import bits_for_levels
+from .multi_tensor import MultiTensorSymbols
 from .quantization.help_functions import huffman_encode
 
 MAGIC = b'QDHUFF\x00\x01'
@@ -151,7 +153,11 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
 
     Exactly one of `s` (uniform, 2 <= s <= 256 levels: one count for all, or a sequence with one entry per QUANTIZED tensor
     in the order of `tensors` -- with quantize_first_last=False the first and the last tensor have no entry) or `points`
-    (non-uniform: one sorted list of at most 256 points per quantized tensor, or one list for all) is given.  quantize_first_last=False stores the first and the last tensor as raw
+    (non-uniform: one sorted list of at most 256 points per quantized tensor, or one list for all) is given.  bucket_size: None,
+    one positive int for all, or -- as `s` -- a sequence of positive ints with one entry per quantized tensor
+    (multi_tensor.per_channel_bucket_sizes(...) of the quantized tensors: the scales a per-channel model trained with); the file
+    stores each tensor's own.  With a sequence, uniform mode on a HIP device takes the symbols, alpha and beta of the whole model
+    from one launch (MultiTensorSymbols); the report's 'symbolizer' names it, 'per_tensor' otherwise.  quantize_first_last=False stores the first and the last tensor as raw
     fp32 (the reference's quantizeFirstLastLayer).  `buffers` (e.g. BN running statistics) are stored as raw fp32.  The
     quantizer options are the ones the training loops save with: linear scaling, deterministic rounding, no mean subtraction,
     no max_element; any other raises ValueError."""
@@ -160,7 +166,16 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
                          'subtraction or max_element')
     if (s is None) == (points is None):
         raise ValueError('give exactly one of s (uniform) or points (non-uniform)')
-    if bucket_size is not None and (isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0):
+    b_list = None                       # the entries of a sequence bucket_size
+    if bucket_size is not None and not isinstance(bucket_size, numbers.Real):
+        if isinstance(bucket_size, (str, bytes)) or not hasattr(bucket_size, '__iter__'):
+            raise ValueError(_BUCKET_RULE)
+        b_list = list(bucket_size)
+        for v in b_list:
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 < v < 2 ** 63:
+                raise ValueError('%s, got the entry %r' % (_BUCKET_RULE, v))
+        b_list = [int(v) for v in b_list]
+    elif bucket_size is not None and (isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0):
         raise ValueError('bucket_size must be a positive int or None')
     s_list = None                       # the entries of a sequence s
     if s is not None:
@@ -188,21 +203,30 @@ def save_compressed(path, tensors, *, s=None, points=None, bucket_size=256, quan
     pts = _point_list(points, len(quant)) if mode else None
     if s_list is not None and len(s_list) != len(quant):
         raise ValueError('s has %d entries for %d quantized tensors: need one per quantized tensor' % (len(s_list), len(quant)))
+    if b_list is not None and len(b_list) != len(quant):
+        raise ValueError('%s: got %d entries for %d quantized tensors' % (_BUCKET_RULE, len(b_list), len(quant)))
     if mode == 0:
         s = [int(v) for v in s_list] if s_list is not None else [int(s)] * len(quant)
     if dev.type == 'cuda':
         with torch.cuda.device(dev):
-            return _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev)
-    return _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev)
+            return _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev, b_list)
+    return _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev, b_list)
 
 
-def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
+_BUCKET_RULE = ('bucket_size must be a positive int, None, or a sequence of positive ints with one entry per quantized tensor '
+                '(in the order of `tensors`)')
+
+
+def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev, b_list=None):
+    """b_list: None, or the bucket size of every quantized tensor (a sequence bucket_size); bks holds tensor j's either way."""
     cuda = dev.type == 'cuda'
+    bks = b_list if b_list is not None else [bucket_size] * len(quant)
+    one_launch = b_list is not None and mode == 0 and cuda and len(quant) > 0
     lib = _lib.load() if cuda else _lib.host()
     qset = set(quant)
     qx = [params[i][1].contiguous().view(-1) for i in quant]
     ns = [x.numel() for x in qx]
-    nbs = [_nbuckets(n, bucket_size) for n in ns]
+    nbs = [_nbuckets(n, b) for n, b in zip(ns, bks)]
     levels = s if mode == 0 else [p.numel() for p in pts]         # mode 0: s is the list of level counts, one per quantized tensor
     sym_off, o = [], 0
     for n in ns:
@@ -211,18 +235,21 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
     nsym, nbuckets = sum(ns), sum(nbs)
     sym = torch.zeros(max(o, SYM_ALIGN), dtype=torch.uint8, device=dev)
     ab = torch.empty(2, max(nbuckets, 1), dtype=torch.float32, device=dev)
-    scratch = torch.empty(max(ns + [1]), dtype=torch.float32, device=dev)
+    scratch = None if one_launch else torch.empty(max(ns + [1]), dtype=torch.float32, device=dev)     # the loop's unread fp32 result
     ws = _lib.workspace(dev) if cuda else None
     wsp, wsn = (ws.data_ptr(), ws.numel()) if cuda else (None, 0)
     st = _lib.stream_ptr(dev) if cuda else None
     fb = 0
     first_bucket = []
+    if one_launch:                      # symbols, alpha and beta of every tensor from one launch, written where the loop writes them
+        MultiTensorSymbols(qx, levels, b_list, symbols=[sym[o:o + n] for o, n in zip(sym_off, ns)],
+                           alpha_beta=(ab[0], ab[1])).encode()
     for j, x in enumerate(qx):
         first_bucket.append(fb)
         n = ns[j]
-        if n:
+        if n and not one_launch:
             a_p, b_p = ab[0].data_ptr() + 4 * fb, ab[1].data_ptr() + 4 * fb
-            bk = bucket_size or 0
+            bk = bks[j] or 0
             if mode == 0:               # K1 with its uint8 level output: the symbols and the alpha / beta of uniformQuantization
                 _lib.check(lib.qd_uniform_f32(x.data_ptr(), scratch.data_ptr(), n, bk, levels[j], a_p, b_p,
                                               sym.data_ptr() + sym_off[j], None, 0, 0.0, 0, 0, wsp, wsn, st), lib)
@@ -300,7 +327,7 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
     for i, (name, t) in enumerate(params):
         if i in qset:
             j = qpos[i]
-            entries.append((name, KIND_QUANTIZED, tuple(t.shape), ns[j], bucket_size or 0, levels[j], first_bucket[j], nbs[j],
+            entries.append((name, KIND_QUANTIZED, tuple(t.shape), ns[j], bks[j] or 0, levels[j], first_bucket[j], nbs[j],
                             int(first_point[j]), int(first_chunk[j])))
         else:
             entries.append((name, KIND_RAW, tuple(t.shape), t.numel(), 0, 0, raw_off[name], t.numel(), 0, 0))
@@ -328,11 +355,16 @@ def _save(path, params, bufs, quant, mode, s, pts, bucket_size, dev):
         ('header', HEADER.size), ('table', len(table_b)), ('code_lengths', 256), ('alpha_beta', 8 * nbuckets),
         ('points', 4 * len(pts_np)), ('raw', 4 * n_raw_params), ('buffers', 4 * n_buf),
         ('chunk_offsets', len(body[6])), ('bitstream', len(body[7]))])
-    ref = n_raw_params * 4 + mean_bits * nsym / 8 + (nsym / bucket_size * 8 if bucket_size is not None else 0)
+    if b_list is not None:              # the reference's bucket term per tensor, summed exactly: [b] * T gives the scalar's value
+        bucket_term = float(sum(fractions.Fraction(n, b) for n, b in zip(ns, b_list)) * 8)
+    else:
+        bucket_term = nsym / bucket_size * 8 if bucket_size is not None else 0
+    ref = n_raw_params * 4 + mean_bits * nsym / 8 + bucket_term
     return {'path': str(path), 'sections': sections, 'file_bytes': sum(sections.values()), 'coding': CODINGS[coding],
             'mode': MODES[mode], 'mean_bit_length': mean_bits, 'code_bits': code_bits, 'quantized_elements': nsym,
             'buckets': nbuckets, 'chunks': nchunks, 'max_code_length': max(lens),
-            'reference_size_mb': ref / 1e6}
+            'reference_size_mb': ref / 1e6,
+            'symbolizer': MultiTensorSymbols.ENTRY_POINT if one_launch else 'per_tensor'}
 
 
 def _pack_table(entries):

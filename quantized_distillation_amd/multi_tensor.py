@@ -1,6 +1,6 @@
 """One-launch forms of the per-parameter loops of the training steps: quantization of every parameter tensor of a
-model (MultiTensorQuantizer), differentiable quantization (MultiTensorDiffQuant) and the bucket-aware STE backward
-(MultiTensorSTE).
+model (MultiTensorQuantizer), differentiable quantization (MultiTensorDiffQuant), the bucket-aware STE backward
+(MultiTensorSTE) and the symbols a compressed checkpoint stores (MultiTensorSymbols).
 
 The reference's training loops quantize parameter by parameter
 (cnn_models/conv_forward_model.py:235-247, translation_models/model.py:247-258):
@@ -596,3 +596,85 @@ class MultiTensorSTE(_DeviceTable):
         return self._launch(lambda: self._entry('qd_multi_ste_backward_f32')(
             self._table.data_ptr(), self.n_tensors, self._tiles, self.bucket_size, self._s, self.tie_mode,
             _lib.stream_ptr(self.device)), self.outs, check_pointers)
+
+
+class MultiTensorSymbols(_DeviceTable):
+    """What a compressed checkpoint stores of uniformly quantized tensors, for ALL tensors of a model in one launch
+    (qd_multi_uniform_symbols_u8, include/qd_hip.h): the uint8 level index of every weight and the (alpha, beta) of every
+    bucket, without the fp32 result.  Tensor i equals, bit for bit, the level indices, alpha and beta of
+    uniformQuantization(t_i, s_i, bucket_size=bucket_size[i]) -- deterministic rounding, no clamp, no mean: the configuration
+    save_compressed stores, and the call it makes for a bucket_size given per tensor.
+
+    s: one level count or a sequence with one entry per tensor, each in 2 .. 256 (a symbol is a byte).
+    bucket_size: one positive int for every tensor, or a sequence of positive ints with one entry per tensor
+    (per_channel_bucket_sizes(tensors) gives the list for one scale pair per output channel); `self.bucket_size` keeps the
+    tuple.  None -- whole-tensor scaling -- is not offered: NotImplementedError (the per-tensor call does it).
+    symbols: optional list of contiguous uint8 device tensors of the tensors' sizes (any alignment); allocated by default.
+    alpha_beta: optional pair of flat contiguous fp32 device tensors that receive alpha and beta (at least `buckets_total`
+    elements each); allocated by default.
+
+    `alpha` / `beta`: lists of fp32 views [nb_i] into the two flat tensors, in table order -- the layout of a compressed file's
+    alpha and beta sections; `buckets_total` their total length.  encode() makes the one launch and returns `symbols`;
+    `entry_point` names the C entry point once it ran."""
+    _DESC = _lib.QdSymbolDesc
+    _WATCH = ('inputs', 'symbols')
+    ENTRY_POINT = 'qd_multi_uniform_symbols_u8'
+
+    def __init__(self, tensors, s, bucket_size, symbols=None, alpha_beta=None):
+        s, tensors = _level_counts(s, tensors)
+        if any(v > 256 for v in (s if isinstance(s, tuple) else (s,))):
+            raise ValueError('s must be an integer in 2 .. 256 (a symbol is one byte), or a sequence of them with one entry per '
+                             'tensor')
+        if bucket_size is None:
+            raise NotImplementedError('MultiTensorSymbols needs a bucket_size: whole-tensor scaling (bucket_size=None) keeps the '
+                                      'per-tensor call')
+        if _is_bucket_list(bucket_size):
+            bucket_size, tensors = _bucket_sizes(bucket_size, tensors)
+        else:
+            if isinstance(bucket_size, bool) or not isinstance(bucket_size, int) or bucket_size <= 0:
+                raise ValueError('bucket_size must be a positive integer, or a sequence of positive integers with one entry per '
+                                 'tensor')
+            tensors = list(tensors)
+            bucket_size = (bucket_size,) * len(tensors)
+        self.bucket_size = bucket_size
+        self._flat = None if alpha_beta is None else tuple(alpha_beta)
+        if self._flat is not None and len(self._flat) != 2:
+            raise ValueError('alpha_beta: a pair of flat float32 tensors')
+        if symbols is None:
+            (self.inputs,) = self._adopt(tensors=tensors)
+            self.symbols = [torch.empty(t.numel(), dtype=torch.uint8, device=self.device) for t in self.inputs]
+        else:
+            self.inputs, self.symbols = self._adopt(tensors=tensors, symbols=symbols, dtypes={'symbols': torch.uint8})
+        for t in self._flat or ():
+            _lib.require_device_f32(t, 'alpha_beta')
+            if not t.is_contiguous() or t.dim() != 1 or t.device != self.device:
+                raise ValueError('alpha_beta: flat contiguous tensors on the device of the tensors')
+        self._bind_levels(s)
+        self._own_levels(len(self.inputs))
+        self._plan()
+
+    def _columns(self):
+        return ('x', self.inputs), ('sym', self.symbols)
+
+    def _plan_table(self, host, n):
+        sizes = (ctypes.c_int64 * n)(*self.bucket_size)
+        tiles, total = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.load().qd_multi_symbols_plan(host, sizes, n, ctypes.byref(tiles), ctypes.byref(total)))
+        self._buckets = torch.tensor(self.bucket_size, dtype=torch.int64, device=self.device)
+        self.buckets_total = int(total.value)
+        if self._flat is None:             # the object's own (kept over a re-plan: the sizes cannot have changed)
+            self._flat = tuple(torch.empty(max(self.buckets_total, 1), dtype=torch.float32, device=self.device) for _ in range(2))
+        if any(t.numel() < self.buckets_total for t in self._flat):
+            raise ValueError('alpha_beta: %d buckets need %d elements each' % (self.buckets_total, self.buckets_total))
+        first = [host[i].first_bucket for i in range(n)] + [self.buckets_total]
+        self.alpha, self.beta = ([t[first[i]:first[i + 1]] for i in range(n)] for t in self._flat)
+        return int(tiles.value)
+
+    def encode(self, check_pointers=True):
+        """Symbols, alpha and beta of all tensors (one launch).  Returns the list of symbol tensors."""
+        out = self._launch(lambda: self._entry(self.ENTRY_POINT)(
+            self._table.data_ptr(), self._levels.data_ptr(), self._buckets.data_ptr(), self.n_tensors, self._tiles,
+            self._flat[0].data_ptr(), self._flat[1].data_ptr(), _lib.stream_ptr(self.device)), self.symbols, check_pointers)
+        if self._tiles > 0:
+            _lib.mark_written(list(self._flat))
+        return out
