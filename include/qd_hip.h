@@ -244,7 +244,9 @@ int qd_bucket_argminmax_f32(const float* x, int64_t n, int64_t bucket, const flo
  *                   only `points` change, quant_functions.py:449-469).
  * points: [k] sorted ascending, device.  assign_mode: QD_ASSIGN_DISTANCE (searchsorted-left +
  * strictly-closer-lower rule, :267-273) or QD_ASSIGN_MIDPOINT (#{midpoints <= u}, the
- * SearchSorted.query formulation, :531-573).
+ * SearchSorted.query formulation, :531-573).  Each rule is defined by where a tie goes; tests/nearest_cases.py with
+ * tests/test_nearest_cases_host.py (libqd_host.so, and each kernel by the plan) and tests/test_hip_nearest_ties.py (every
+ * kernel of libqd_hip.so) pin both on points, midpoints, cell boundaries and their fp32 neighbours.
  * q: [n] = points[idx]*alpha + beta (+mean).  idx: optional, idx_bytes 8 (int64, what the
  * reference API returns) or 1 (uint8, k <= 256).  A NaN u -- every element of a bucket whose alpha or beta is NaN --
  * has index k - 1 (np.searchsorted orders a NaN last, :267-268 and :572) and value NaN.

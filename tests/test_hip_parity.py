@@ -657,10 +657,12 @@ def test_fine_cell_table_with_crowded_and_degenerate_points(k):
     """Above 32 points the pre-processed forward (midpoint rule) answers an element from a 2048-cell table when its cell holds
     at most one midpoint and searches inside the cell otherwise (qd_transform.h).  Point sets that stress exactly that:
     all points inside ONE cell, a bell-shaped crowd (what a percentile initialisation produces), duplicates, points ON cell
-    boundaries j / 2048, points outside [0, 1]; values on boundaries, on midpoints, below 0, above 1, +-inf and NaN -- on the
-    vector kernel (bucket 256), one wave per bucket (1000), the chunk kernels (100, 33: coarse table), lane groups (a short
-    tensor) and the single-bucket kernels.  Indices and values bit-identical to numpy's count of midpoints <= u
-    (ref: quant_functions.py:531-563)."""
+    boundaries j / 2048, points outside [0, 1]; values on boundaries, on midpoints, below 0, above 1, +-inf and NaN.  Every
+    call here is pre-scaled, so what qd_transform_plan names for it is k_nearest_prescaled_stream (every bucket size with more
+    than one bucket -- 256, 1000, 100, 33, 5000, and 256 on 700 elements -- and every indices-only call) and k_single_apply
+    (one bucket, 200003 and 50000 elements, with q).  The bucket kernels -- vector, one wave per bucket, chunk, lane groups,
+    generic -- meet such point sets, under both rules, in tests/test_hip_nearest_ties.py.  Indices and values bit-identical to numpy's
+    count of midpoints <= u (ref: quant_functions.py:531-563)."""
     lib = _lib.load()
     rng = np.random.RandomState(k)
     sets = {
