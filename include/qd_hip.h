@@ -19,6 +19,12 @@
  *                                 x[n-1] (padding never changes min/max, so kernels ignore it);
  *   - all calls are asynchronous on `stream` (a hipStream_t passed as void*), never allocate,
  *     never synchronise with the host;
+ *   - capture rule: every call that launches can therefore be recorded into a hipGraph (after one eager call of the same
+ *     entry point on that stream).  By-value arguments and HOST arrays are frozen at record time; device memory -- inputs,
+ *     descriptor tables, code books, `mean`, the workspace -- is read at replay time, and the workspace still needs no
+ *     initialisation.  A refused call (negative return) records nothing and leaves the capture valid.  The one-launch
+ *     single-bucket kernel is not recorded: a capturing stream takes the three-launch path, with the same bits
+ *     (tests/test_hip_capture_abi.py replays every entry point on other data);
  *   - return value: 0 on success, a positive hipError_t if a launch failed, or a negative
  *     QD_ERR_* code for argument errors.  qd_error_string() describes either.
  *   - optional outputs may be NULL.
@@ -695,7 +701,9 @@ int qd_huffman_decode_f32(const uint32_t* words, int64_t nwords, const uint32_t*
  *   either sign bit and any payload, orders last -- after +inf -- and a rank among the NaNs returns a NaN, not the bits of
  *   a particular one; -0 before +0), found by a 12|10|10-bit radix SELECT: x is read three times and never sorted or modified.
  *   ranks is a HOST array of m non-decreasing values in [0, n); 1 <= m <= QD_ORDER_STATS_MAX_RANKS; n < 2^32
- *   (QD_ERR_UNSUPPORTED beyond either).  workspace: qd_order_stats_workspace_bytes(m) bytes of device memory. */
+ *   (QD_ERR_UNSUPPORTED beyond either).  workspace: qd_order_stats_workspace_bytes(m) bytes of device memory.
+ *   ranks is read during the call and never again: it may be freed when the call returns, and a captured launch replays
+ *   the ranks it was recorded with on the x of the moment. */
 #define QD_ORDER_STATS_MAX_RANKS 32
 size_t qd_order_stats_workspace_bytes(int m);
 int qd_order_stats_f32(const float* x, int64_t n, const int64_t* ranks, int m, float* out, void* workspace,
