@@ -36,7 +36,7 @@ def _tmp(path):
 
 
 SOURCES = ['qd_kernels.hip', 'qd_nearest.hip', 'qd_reductions.hip', 'qd_scale.hip', 'qd_codec.hip', 'qd_multi_dq.hip', 'qd_abs.hip', 'qd_multi_uniform.hip',
-           'qd_select.hip', 'qd_selftest.hip', 'qd_huffman.hip', 'qd_multi_uniform_out16.hip', 'qd_multi_symbols.hip']
+           'qd_select.hip', 'qd_selftest.hip', 'qd_huffman.hip', 'qd_multi_uniform_out16.hip', 'qd_multi_symbols.hip', 'qd_ste.hip']
 OBJ_DIR = os.path.join(os.path.dirname(_lib.INCLUDE), 'build', 'obj')              # git-ignored; objects are rebuilt from source when stale
 
 

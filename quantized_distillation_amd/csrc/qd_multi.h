@@ -1,4 +1,4 @@
-// qd_multi.h -- what the multi-tensor launches share (qd_multi_uniform.hip, qd_multi_dq.hip, k_multi_ste in qd_reductions.hip).
+// qd_multi.h -- what the multi-tensor launches share (qd_multi_uniform.hip, qd_multi_dq.hip, qd_ste.hip).
 //
 // Each of them runs over a device table of per-tensor descriptors (QdTensorDesc, QdDiffQuantDesc, QdSteDesc; include/qd_hip.h)
 // that the host plan has cut into work items ("tiles"): a descriptor's prefix field holds the number of items of the tensors

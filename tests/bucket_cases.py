@@ -4,7 +4,7 @@ tests/test_bucket_cases_host.py (the plans, the expected bits from libqd_host.so
 tests/test_hip_multi_buckets.py (the kernels, bit for bit).  A plain helper module: no fixtures, nothing runs on import.
 
 Every case is (n, bucket, s), a data recipe, the 4-byte phase it sits at inside a 16-byte granule and the PATH it is meant to
-reach.  q_rule() / ste_rule() restate the tile rule of csrc/qd_multi.h (bucket_tiles) and of ste_cut (csrc/qd_reductions.hip) in
+reach.  q_rule() / ste_rule() restate the tile rule of csrc/qd_multi.h (bucket_tiles) and of ste_cut (csrc/qd_ste.hip) in
 Python; check_paths() asserts for every case that the restated rule sends it where the case says, so a case that silently lands
 on another body fails on the CPU.  The shapes are the smallest that reach each path: a few thousand elements, but for the one
 row longer than 64 Ki elements."""

@@ -4,10 +4,10 @@
     python tools/device_code_diff.py OTHER_libqd_hip.so [THIS_libqd_hip.so]
 
 For a change that touches host code only (a launcher, a header split) the answer must be yes: that is its whole speed argument.
-For every gfx950 code object both libraries embed (tools/kernel_meta.code_objects: one per translation unit, in build order)
-and every function symbol in it, the machine-code bytes are compared, and so are the kernel descriptors (the 64-byte `.kd`
-objects) and the metadata of tools/kernel_meta.kernels (VGPRs, SGPRs, LDS, scratch, spills).  Symbols may move; they may not
-change.  Exit status 1 on any difference."""
+The function symbols of all gfx950 code objects a library embeds (tools/kernel_meta.code_objects: one per translation unit)
+are pooled by name, and for every name the machine-code bytes are compared, and so are the kernel descriptors (the 64-byte
+`.kd` objects) and the metadata of tools/kernel_meta.kernels (VGPRs, SGPRs, LDS, scratch, spills).  Symbols may move, inside
+a code object or from one translation unit to another; they may not change.  Exit status 1 on any difference."""
 import os
 import struct
 import sys
@@ -65,28 +65,36 @@ def main():
     this = sys.argv[2] if len(sys.argv) > 2 else kernel_meta.os.path.join(HERE, '..', 'quantized_distillation_amd', 'libqd_hip.so')
     a, b = kernel_meta.code_objects(other), kernel_meta.code_objects(this)
     bad = []
-    if len(a) != len(b):
-        bad.append('%d code objects against %d' % (len(a), len(b)))
+
+    def pooled(objs):
+        """{name: bytes} over all code objects of a library: a symbol may move between translation units.  (A kernel of a
+        shared header is emitted by every translation unit that includes it: the same bytes each time.)"""
+        pool = {}
+        for i, img in enumerate(objs):
+            for name, code in symbols(img).items():
+                if name.startswith('__hip_cuid_'):                 # the translation unit's id, a hash of its source text
+                    continue
+                if name in pool and pool[name] != code and not same_but_moved(name, pool[name], code):
+                    bad.append('%s is defined twice with different bytes (again in code object %d)' % (name, i))
+                pool[name] = code
+        return pool
+
+    sx, sy = pooled(a), pooled(b)
     nsym = nbytes = nmoved = 0
-    for i, (x, y) in enumerate(zip(a, b)):
-        sx, sy = symbols(x), symbols(y)
-        for name in sorted(set(sx) | set(sy)):
-            if name.startswith('__hip_cuid_'):                 # the translation unit's id, a hash of its source text
-                continue
-            if name not in sx or name not in sy:
-                bad.append('code object %d: %s only in %s' % (i, name, 'the other library' if name in sx else 'this library'))
-            elif sx[name] != sy[name] and not same_but_moved(name, sx[name], sy[name]):
-                bad.append('code object %d: %s differs (%d / %d bytes)' % (i, name, len(sx[name]), len(sy[name])))
-            else:
-                nsym += 1
-                nbytes += len(sx[name])
-                nmoved += sx[name] != sy[name]
-    key = lambda k: k['name']                                                         # noqa: E731
-    ma, mb = sorted(kernel_meta.kernels(other), key=key), sorted(kernel_meta.kernels(this), key=key)
+    for name in sorted(set(sx) | set(sy)):
+        if name not in sx or name not in sy:
+            bad.append('%s only in %s' % (name, 'the other library' if name in sx else 'this library'))
+        elif sx[name] != sy[name] and not same_but_moved(name, sx[name], sy[name]):
+            bad.append('%s differs (%d / %d bytes)' % (name, len(sx[name]), len(sy[name])))
+        else:
+            nsym += 1
+            nbytes += len(sx[name])
+            nmoved += sx[name] != sy[name]
+    ma, mb = ({k['name']: k for k in kernel_meta.kernels(lib)} for lib in (other, this))
     if ma != mb:
-        bad.append('kernel metadata differs: %s' % [(p, q) for p, q in zip(ma, mb) if p != q][:5])
-    print('%d code objects, %d symbols (%d bytes of code, descriptors and device data) identical -- %d of them up to an encoded '
-          'position (same_but_moved) -- metadata of %d kernels %s' % (len(b), nsym, nbytes, nmoved, len(mb), 'identical' if ma == mb else 'DIFFERENT'))
+        bad.append('kernel metadata differs: %s' % [(ma.get(n), mb.get(n)) for n in sorted(set(ma) | set(mb)) if ma.get(n) != mb.get(n)][:5])
+    print('%d / %d code objects, %d symbols (%d bytes of code, descriptors and device data) identical -- %d of them up to an encoded '
+          'position (same_but_moved) -- metadata of %d kernels %s' % (len(a), len(b), nsym, nbytes, nmoved, len(mb), 'identical' if ma == mb else 'DIFFERENT'))
     print('\n'.join(bad) if bad else 'device code is the same')
     return 1 if bad else 0
 

@@ -2,7 +2,7 @@
 """Which of the kernel instantiations shipped in libqd_hip.so does the GPU test suite actually launch?
 
 The launchers choose among dozens of instantiations per mode by bucket size, alignment, point count and tensor size
-(csrc/qd_plan.h plan_transform, csrc/qd_reductions.hip, csrc/qd_multi_uniform.hip); the tests are parameterised by
+(csrc/qd_plan.h plan_transform, csrc/qd_reductions.hip, csrc/qd_ste.hip, csrc/qd_multi_uniform.hip); the tests are parameterised by
 those INPUTS, not by the kernel that ends up running.
 This tool closes the loop: it runs the parity suite under `rocprofv3 --kernel-trace --stats`, takes the
 names of the kernels that were dispatched, and compares them with the kernels the shipped code objects contain
