@@ -599,9 +599,15 @@ int qd_multi_point_grad_in16_f32(const QdDiffQuantDesc* table, int ntensors, int
  * bucket) and the level histogram behind the Huffman accounting of
  * quantization/help_functions.py:175-232.
  * qd_pack_uniform_f32: quantize x with `levels` levels per bucket and store ONLY the level
- *   indices, `bits` (1, 2, 4 or 8; levels <= 2^bits) per element, element e in bits
+ *   indices, `bits` (any of 1 ... 8; levels <= 2^bits) per element, element e in bits
  *   [e*bits, (e+1)*bits) of `packed` (qd_packed_bytes(n, bits) bytes, little endian inside a byte),
  *   plus alpha/beta [num_buckets] (optional).  bucket in {64,128,256,512,1024,2048}; x 16-byte aligned.
+ *   The stream, for all eight widths: bit i of the stream is bit i & 7 of byte i >> 3; element e holds its index least
+ *   significant bit first in stream bits [e*bits, (e+1)*bits) -- at 3, 5, 6 and 7 bits across a byte or a 32-bit word
+ *   boundary where it falls on one; the unused high bits of the last byte are zero.  Every call of the three entry points
+ *   writes, or reads, exactly qd_packed_bytes(n, bits) bytes of `packed` and not one more (`packed` 4-byte aligned for
+ *   qd_pack_uniform_f32 and qd_unpack_uniform_f32, any alignment for qd_pack_levels_u8; the last partial 32-bit word is
+ *   accessed byte by byte).  qd_pack_levels_u8 masks every symbol to `bits` bits.
  * qd_pack_levels_u8: the same packing for level indices that are already there (the level_idx output of qd_uniform_f32):
  *   together they give the packed form at ANY bucket size, bucket 0 = none included.
  * qd_unpack_uniform_f32: y = (index/(levels-1))*alpha + beta -- bit-identical to the output of

@@ -20,6 +20,17 @@ def bits_for_levels(s):
     raise ValueError('the packed format holds at most 256 levels')
 
 
+def min_bits_for_levels(s):
+    """The smallest width the packed format has for `s` levels (1 ... 8 bits: 5 ... 8 levels take 3, 17 ... 32 take 5):
+    what the reference's size accounting charges per element, where bits_for_levels -- the default of pack_uniform -- rounds
+    up to 1, 2, 4 or 8."""
+    s = _lib.level_count(s)
+    for b in range(1, 9):
+        if s <= (1 << b):
+            return b
+    raise ValueError('the packed format holds at most 256 levels')
+
+
 class PackedUniform(object):
     """`bits`-per-element level indices + per-bucket (alpha, beta) of one tensor."""
 
@@ -51,14 +62,15 @@ def pack_uniform(tensor, s, bucket_size=256, bits=None):
     """Quantize `tensor` with `s` levels per bucket and keep only the packed level indices (+ alpha / beta per bucket).
     Bucket sizes 64 ... 2048 (powers of two) take one fused kernel (4 B read + bits/8 B written per element); any other
     bucket size -- and bucket_size=None -- quantizes with the level-index side output of the quantize kernel and packs
-    those (qd_uniform_f32 + qd_pack_levels_u8): the same bytes, whatever the bucket geometry."""
+    those (qd_uniform_f32 + qd_pack_levels_u8): the same bytes, whatever the bucket geometry.  `bits`: any width from 1 to 8
+    that holds s levels; None takes bits_for_levels(s) (1, 2, 4 or 8), min_bits_for_levels(s) is the smallest."""
     _lib.require_device_f32(tensor)
     if bucket_size is not None and (not isinstance(bucket_size, int) or isinstance(bucket_size, bool) or bucket_size <= 0):
         raise ValueError('Bucket size must be an integer and strictly positive. Pass None if you want to avoid using buckets')
     s = _lib.level_count(s)
     bits = bits_for_levels(s) if bits is None else bits
-    if bits not in (1, 2, 4, 8) or s > (1 << bits):
-        raise ValueError('bits must be 1, 2, 4 or 8 and hold s levels')
+    if not isinstance(bits, int) or isinstance(bits, bool) or not 1 <= bits <= 8 or s > (1 << bits):
+        raise ValueError('bits must be an integer from 1 to 8 and hold s levels (s <= 2**bits)')
     if _lib.on_other_device(tensor):
         with torch.cuda.device(tensor.device):
             return pack_uniform(tensor, s, bucket_size, bits)

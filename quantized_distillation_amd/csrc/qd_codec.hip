@@ -4,13 +4,19 @@
 // helpers/functions.py:226-262 charges  bits*N/8  bytes for the level indices plus 8 bytes
 // (alpha, beta as fp32) per bucket, and quantization/help_functions.py:175-232 computes the Huffman
 // mean code length from the histogram of the level indices.  This file produces exactly that
-// representation on the device -- `bits`-per-element packed level indices + per-bucket alpha/beta --
+// representation on the device -- `bits`-per-element packed level indices (bits = 1 ... 8) + per-bucket alpha/beta --
 // decodes it back to the fake-quantized fp32 tensor (bit-identical to qd_uniform_f32's output),
 // and builds the level histogram without copying the tensor to the host.
 //
 // pack   : read 4 B/elem, write bits/8 B/elem           (HBM-bound on the read)
 // unpack : read bits/8 B/elem, write 4 B/elem            (HBM-bound on the write)
 // hist   : read 1 B/elem (uint8 indices)
+//
+// The stream, for every width b = 1 ... 8: bit i of the stream is bit i & 7 of byte i >> 3, element e holds its index LSB
+// first in stream bits [e b, (e + 1) b), the unused high bits of the last byte are zero, and a call touches exactly
+// qd_packed_bytes(n, b) bytes.  At 1, 2, 4 and 8 bits an element lies inside one byte; at 3, 5, 6 and 7 it may straddle a
+// byte or a 32-bit word (straddles()), and those widths take the branches and kernels marked so below -- the other four
+// compile from the text they always had.
 #include "qd_common.h"
 
 #include <atomic>
@@ -21,10 +27,34 @@ using namespace qd;
 
 namespace {
 
+constexpr bool straddles(int bits) { return bits == 3 || bits == 5 || bits == 6 || bits == 7; }
+
 template <int BITS>
 __device__ __forceinline__ uint32_t pack4(const float (&lev)[4]) {
     return (uint32_t)(int)lev[0] | ((uint32_t)(int)lev[1] << BITS) | ((uint32_t)(int)lev[2] << (2 * BITS)) |
            ((uint32_t)(int)lev[3] << (3 * BITS));
+}
+
+// Straddling widths, fused pack: the LPB lanes of a bucket hold a slab of LPB * 4 consecutive elements, lane l its four codes
+// `pk` = 4 BITS bits at slab bit l * 4 BITS.  The slab is LPB * BITS / 8 whole 32-bit words (a bucket row is a multiple of
+// 64 elements, so it starts word aligned); lane w < LPB * BITS / 8 assembles word w from the three or four lanes whose
+// pieces overlap it (ds_bpermute inside the own bucket's lanes, which are all active) and stores it: every word by exactly
+// one lane, no byte stores, no atomics.
+template <int LPB, int BITS>
+__device__ __forceinline__ void store_slab_words(uint32_t pk, int sub, int l, uint8_t* slab) {
+    constexpr int CH = 4 * BITS;                     // bits per lane
+    constexpr int K = (CH - 1 + 32 + CH - 1) / CH;   // lanes that can overlap one word (4 at 3 bits, else 3)
+    static_assert((K - 1) * CH < 64 && CH - 1 + 32 <= 64, "the pieces of a word are collected in 64 bits");
+    const int first = (32 * l) / CH;                 // the lane that holds the word's first bit
+    const int sh = 32 * l - first * CH;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int src = first + k;
+        const uint32_t c = (uint32_t)__shfl((int)pk, sub * LPB + (src < LPB ? src : LPB - 1));
+        if (src < LPB) acc |= (uint64_t)c << (k * CH);
+    }
+    if (l < LPB * BITS / 8) *(uint32_t*)(slab + 4 * l) = (uint32_t)(acc >> sh);
 }
 
 // LPB lanes per bucket, V float4 per lane (same geometry as k_bucket_vec).  Element e of the
@@ -69,6 +99,8 @@ __global__ __launch_bounds__(256) void k_pack_vec(const float* x, uint8_t* packe
             qdq(v[j].z, a, b, sm1, 0.0f, lev[2]);
             qdq(v[j].w, a, b, sm1, 0.0f, lev[3]);
             const uint32_t pk = pack4<BITS>(lev);
+            if constexpr (straddles(BITS)) store_slab_words<LPB, BITS>(pk, sub, l, packed + (((e - l * 4) * BITS) >> 3));
+            else
             if (BITS == 8) *(uint32_t*)(packed + e) = pk;
             else if (BITS == 4) *(uint16_t*)(packed + (e >> 1)) = (uint16_t)pk;
             else if (BITS == 2) packed[e >> 2] = (uint8_t)pk;
@@ -93,6 +125,23 @@ __global__ __launch_bounds__(64) void k_pack_tail(const float* x, uint8_t* packe
     float a, b;
     alpha_beta(mn, mx, a, b);
     if (lane == 0) { if (alpha) alpha[bkt] = a; if (beta) beta[bkt] = b; }
+    if constexpr (straddles(BITS)) {                 // lo * BITS is a multiple of 8; a byte takes pieces of up to four elements
+        const int64_t byte0 = (lo * BITS) >> 3;
+        const int64_t nb = (((n - lo) * BITS) + 7) >> 3;
+        for (int64_t t = lane; t < nb; t += 64) {
+            int64_t e = lo + (t * 8) / BITS;         // the element that holds the byte's first bit
+            int pos = (int)((e - lo) * BITS - t * 8);    // where its bit 0 falls relative to the byte's: -(BITS - 1) ... 0
+            uint32_t byte = 0;
+            for (; pos < 8 && e < n; ++e, pos += BITS) {
+                float lev;
+                qdq(x[e], a, b, sm1, 0.0f, lev);
+                const uint32_t c = (uint32_t)(int)lev;
+                byte |= pos >= 0 ? c << pos : c >> -pos;
+            }
+            packed[byte0 + t] = (uint8_t)byte;
+        }
+        return;
+    }
     constexpr int EPB = 8 / BITS;                    // elements per byte
     const int64_t first_byte = (lo * BITS) >> 3;     // lo is a multiple of the bucket (>= 64)
     const int64_t nbytes = (((n - lo) * BITS) + 7) >> 3;
@@ -111,6 +160,23 @@ __global__ __launch_bounds__(64) void k_pack_tail(const float* x, uint8_t* packe
     }
 }
 
+// Straddling widths, decode: group g of four elements is 4 BITS <= 28 bits from stream bit 4 BITS g on; they come back in
+// the low bits (what lies above them belongs to the next group: the caller masks).  Two aligned 32-bit loads and a 64-bit
+// shift where both words lie wholly inside the stream of `nbytes` bytes, byte by byte (five at the most) at its end.
+template <int BITS>
+__device__ __forceinline__ uint32_t group_bits(const uint8_t* packed, int64_t g, int64_t nbytes) {
+    const int64_t p = g * (4 * BITS);
+    const int64_t w = p >> 5;
+    if ((w + 2) * 4 <= nbytes) {
+        const uint32_t lo = ((const uint32_t*)packed)[w], hi = ((const uint32_t*)packed)[w + 1];
+        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (p & 31));
+    }
+    uint64_t acc = 0;
+    const int64_t b0 = p >> 3;
+    for (int c = 0; c < 5 && b0 + c < nbytes; ++c) acc |= (uint64_t)packed[b0 + c] << (8 * c);
+    return (uint32_t)(acc >> (p & 7));
+}
+
 // decode: each thread expands 4 consecutive elements into ONE float4 (lanes contiguous: a wave
 // writes 1 KiB per store instruction); the packed read is 4*BITS bits per lane
 template <int BITS>
@@ -127,6 +193,8 @@ __global__ __launch_bounds__(256) void k_unpack(const uint8_t* packed, float* y,
         const float a = alpha[bkt], b = beta[bkt];
         uint32_t bits;
         const bool full = e0 + 4 <= n;
+        if constexpr (straddles(BITS)) bits = group_bits<BITS>(packed, gI, (n * BITS + 7) >> 3);
+        else
         if (BITS == 8) {
             if (full) bits = *(const uint32_t*)(packed + e0);
             else { bits = 0; for (int64_t c = 0; e0 + c < n; ++c) bits |= (uint32_t)packed[e0 + c] << (8 * c); }
@@ -206,6 +274,58 @@ __global__ __launch_bounds__(256) void k_pack_levels(const uint8_t* lev, int64_t
     }
 }
 
+// k_pack_levels for the straddling widths: every thread turns 32 levels into BITS whole words (32 levels start word aligned
+// at any width); the levels after the last whole group of 32 byte by byte, straddling included.  The 16-byte loads and the
+// word stores under the same alignment condition as above, bytes otherwise.
+template <int BITS>
+__global__ __launch_bounds__(256) void k_pack_levels32(const uint8_t* lev, int64_t n, uint8_t* packed) {
+    constexpr uint32_t MASK = (1u << BITS) - 1u;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+    const int64_t ngroups = n >> 5;
+    const bool vec = ((((uintptr_t)lev) & 15) == 0) && ((((uintptr_t)packed) & 3) == 0);
+    for (int64_t g = tid; g < ngroups; g += nth) {
+        const uint8_t* src = lev + 32 * g;
+        uint8_t* dst = packed + 4 * BITS * g;
+        uint32_t in[8];
+        if (vec) {
+            const uint4 t0 = *(const uint4*)src, t1 = *(const uint4*)(src + 16);
+            in[0] = t0.x; in[1] = t0.y; in[2] = t0.z; in[3] = t0.w; in[4] = t1.x; in[5] = t1.y; in[6] = t1.z; in[7] = t1.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                in[q] = (uint32_t)src[4 * q] | ((uint32_t)src[4 * q + 1] << 8) | ((uint32_t)src[4 * q + 2] << 16) | ((uint32_t)src[4 * q + 3] << 24);
+        }
+        uint64_t acc = 0;
+        int fill = 0, k = 0;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) {
+            acc |= (uint64_t)((in[c >> 2] >> (8 * (c & 3))) & MASK) << fill;
+            fill += BITS;
+            if (fill >= 32) {
+                const uint32_t word = (uint32_t)acc;
+                if (vec) *(uint32_t*)(dst + 4 * k) = word;
+                else {
+                    dst[4 * k] = (uint8_t)word; dst[4 * k + 1] = (uint8_t)(word >> 8);
+                    dst[4 * k + 2] = (uint8_t)(word >> 16); dst[4 * k + 3] = (uint8_t)(word >> 24);
+                }
+                acc >>= 32; fill -= 32; ++k;
+            }
+        }
+    }
+    if (tid == 0) {                                  // the levels after the last whole group
+        uint8_t* dst = packed + 4 * BITS * ngroups;
+        uint32_t acc = 0;
+        int fill = 0;
+        for (int64_t e = ngroups << 5; e < n; ++e) {
+            acc |= ((uint32_t)lev[e] & MASK) << fill;
+            fill += BITS;
+            if (fill >= 8) { *dst++ = (uint8_t)acc; acc >>= 8; fill -= 8; }
+        }
+        if (fill > 0) *dst = (uint8_t)acc;
+    }
+}
+
 // decode for ANY bucket size (bucket == 0: one alpha / beta for the tensor): as k_unpack, the bucket of every element from
 // one 32- or 64-bit division per group of four
 template <int BITS>
@@ -226,6 +346,8 @@ __global__ __launch_bounds__(256) void k_unpack_any(const uint8_t* packed, float
         }
         uint32_t bits;
         const bool full = e0 + 4 <= n;
+        if constexpr (straddles(BITS)) bits = group_bits<BITS>(packed, gI, (n * BITS + 7) >> 3);
+        else
         if (BITS == 8) {
             if (full) bits = *(const uint32_t*)(packed + e0);
             else { bits = 0; for (int64_t c = 0; e0 + c < n; ++c) bits |= (uint32_t)packed[e0 + c] << (8 * c); }
@@ -671,6 +793,21 @@ __global__ __launch_bounds__(256) void k_zero_u64(unsigned long long* p, int n) 
     for (int i = threadIdx.x; i < n; i += 256) p[i] = 0ull;
 }
 
+// f(std::integral_constant<int, bits>()) for bits = 1 ... 8: the launchers pick their instantiation through it
+template <typename F>
+inline void for_bits(int bits, F&& f) {
+    switch (bits) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: f(std::integral_constant<int, 5>()); break;
+        case 6: f(std::integral_constant<int, 6>()); break;
+        case 7: f(std::integral_constant<int, 7>()); break;
+        default: f(std::integral_constant<int, 8>()); break;
+    }
+}
+
 inline int blocks_for(int64_t items, int per_block, int cap) {
     return grid_blocks(items, per_block, cap);                 // (qd_common.h: the site's own cap and the grid-cap hook)
 }
@@ -683,7 +820,7 @@ int64_t qd_packed_bytes(int64_t n, int bits) { return n < 0 || bits < 1 ? -1 : (
 
 int qd_pack_uniform_f32(const float* x, int64_t n, int64_t bucket, int levels, int bits, uint8_t* packed, float* alpha,
                         float* beta, void* stream) {
-    if (n < 0 || levels < 2 || (bits != 1 && bits != 2 && bits != 4 && bits != 8) || levels > (1 << bits))
+    if (n < 0 || levels < 2 || bits < 1 || bits > 8 || levels > (1 << bits))
         return QD_ERR_INVALID_ARGUMENT;
     if (n > 0 && (!x || !packed)) return QD_ERR_INVALID_ARGUMENT;      // alpha / beta: optional outputs
     if (bucket != 64 && bucket != 128 && bucket != 256 && bucket != 512 && bucket != 1024 && bucket != 2048)
@@ -697,10 +834,9 @@ int qd_pack_uniform_f32(const float* x, int64_t n, int64_t bucket, int levels, i
     {                                                                                                                \
         const int64_t tiles = (nfull + (64 / LPB) - 1) / (64 / LPB);                                                 \
         const int blocks = blocks_for(tiles, 4, kNoOwnCap);                                                            \
-        if (bits == 8) hipLaunchKernelGGL((k_pack_vec<LPB, V, 8>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
-        else if (bits == 4) hipLaunchKernelGGL((k_pack_vec<LPB, V, 4>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
-        else if (bits == 2) hipLaunchKernelGGL((k_pack_vec<LPB, V, 2>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
-        else hipLaunchKernelGGL((k_pack_vec<LPB, V, 1>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
+        for_bits(bits, [&](auto B) {                                                                                 \
+            hipLaunchKernelGGL((k_pack_vec<LPB, V, decltype(B)::value>), dim3(blocks), dim3(256), 0, st, x, packed, alpha, beta, nfull, sm1); \
+        });                                                                                                          \
     }
     if (nfull > 0) {
         switch (bucket) {
@@ -715,30 +851,30 @@ int qd_pack_uniform_f32(const float* x, int64_t n, int64_t bucket, int levels, i
 #undef QD_PACK
     if (nfull * bucket < n) {
         const int64_t lo = nfull * bucket;
-        if (bits == 8) hipLaunchKernelGGL(k_pack_tail<8>, dim3(1), dim3(64), 0, st, x, packed, alpha, beta, lo, n, nfull, sm1);
-        else if (bits == 4) hipLaunchKernelGGL(k_pack_tail<4>, dim3(1), dim3(64), 0, st, x, packed, alpha, beta, lo, n, nfull, sm1);
-        else if (bits == 2) hipLaunchKernelGGL(k_pack_tail<2>, dim3(1), dim3(64), 0, st, x, packed, alpha, beta, lo, n, nfull, sm1);
-        else hipLaunchKernelGGL(k_pack_tail<1>, dim3(1), dim3(64), 0, st, x, packed, alpha, beta, lo, n, nfull, sm1);
+        for_bits(bits, [&](auto B) {
+            hipLaunchKernelGGL(k_pack_tail<decltype(B)::value>, dim3(1), dim3(64), 0, st, x, packed, alpha, beta, lo, n, nfull, sm1);
+        });
     }
     return (int)hipGetLastError();
 }
 
 int qd_pack_levels_u8(const uint8_t* levels_idx, int64_t n, int bits, uint8_t* packed, void* stream) {
-    if (n < 0 || (bits != 1 && bits != 2 && bits != 4 && bits != 8) || (n > 0 && (!levels_idx || !packed)))
+    if (n < 0 || bits < 1 || bits > 8 || (n > 0 && (!levels_idx || !packed)))
         return QD_ERR_INVALID_ARGUMENT;
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int blocks = blocks_for(n / (32 / bits) + 1, 256 * 4, kNoOwnCap);
-    if (bits == 8) hipLaunchKernelGGL(k_pack_levels<8>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
-    else if (bits == 4) hipLaunchKernelGGL(k_pack_levels<4>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
-    else if (bits == 2) hipLaunchKernelGGL(k_pack_levels<2>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
-    else hipLaunchKernelGGL(k_pack_levels<1>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
+    const int blocks = blocks_for(n / (straddles(bits) ? 32 : 32 / bits) + 1, 256 * 4, kNoOwnCap);     // a thread per word / per 32 levels
+    for_bits(bits, [&](auto B) {
+        constexpr int BITS = decltype(B)::value;
+        if constexpr (straddles(BITS)) hipLaunchKernelGGL(k_pack_levels32<BITS>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
+        else hipLaunchKernelGGL(k_pack_levels<BITS>, dim3(blocks), dim3(256), 0, st, levels_idx, n, packed);
+    });
     return (int)hipGetLastError();
 }
 
 int qd_unpack_uniform_f32(const uint8_t* packed, int64_t n, int64_t bucket, int levels, int bits, const float* alpha,
                           const float* beta, float* y, void* stream) {
-    if (n < 0 || levels < 2 || (bits != 1 && bits != 2 && bits != 4 && bits != 8) || levels > (1 << bits))
+    if (n < 0 || levels < 2 || bits < 1 || bits > 8 || levels > (1 << bits))
         return QD_ERR_INVALID_ARGUMENT;
     if (n > 0 && (!packed || !y || !alpha || !beta)) return QD_ERR_INVALID_ARGUMENT;
     if (bucket < 0) return QD_ERR_INVALID_ARGUMENT;
@@ -750,10 +886,9 @@ int qd_unpack_uniform_f32(const uint8_t* packed, int64_t n, int64_t bucket, int 
         const float sm1b = (float)(levels - 1);
         const int64_t bk = (bucket == 0 || n < bucket) ? 0 : bucket;
         const int blocks2 = blocks_for((n + 3) / 4, 256 * 4, kNoOwnCap);
-        if (bits == 8) hipLaunchKernelGGL(k_unpack_any<8>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
-        else if (bits == 4) hipLaunchKernelGGL(k_unpack_any<4>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
-        else if (bits == 2) hipLaunchKernelGGL(k_unpack_any<2>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
-        else hipLaunchKernelGGL(k_unpack_any<1>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
+        for_bits(bits, [&](auto B) {
+            hipLaunchKernelGGL(k_unpack_any<decltype(B)::value>, dim3(blocks2), dim3(256), 0, st2, packed, y, alpha, beta, n, bk, sm1b);
+        });
         return (int)hipGetLastError();
     }
     int row_shift = 0;
@@ -761,10 +896,9 @@ int qd_unpack_uniform_f32(const uint8_t* packed, int64_t n, int64_t bucket, int 
     hipStream_t st = (hipStream_t)stream;
     const float sm1 = (float)(levels - 1);
     const int blocks = blocks_for((n + 3) / 4, 256 * 4, kNoOwnCap);
-    if (bits == 8) hipLaunchKernelGGL(k_unpack<8>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
-    else if (bits == 4) hipLaunchKernelGGL(k_unpack<4>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
-    else if (bits == 2) hipLaunchKernelGGL(k_unpack<2>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
-    else hipLaunchKernelGGL(k_unpack<1>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
+    for_bits(bits, [&](auto B) {
+        hipLaunchKernelGGL(k_unpack<decltype(B)::value>, dim3(blocks), dim3(256), 0, st, packed, y, alpha, beta, n, row_shift, sm1);
+    });
     return (int)hipGetLastError();
 }
 
