@@ -22,11 +22,9 @@ def hipcc():
 
 def _headers():
     """What every object / assembly file depends on besides its own source (ONE list for build_extension and
-    device_assembly: qd_transform.h holds almost all kernel code)."""
-    return [os.path.join(_lib.CSRC, 'qd_common.h'), os.path.join(_lib.CSRC, 'qd_plan.h'), os.path.join(_lib.CSRC, 'qd_transform.h'),
-            os.path.join(_lib.CSRC, 'qd_multi.h'), os.path.join(_lib.CSRC, 'qd_multi_uniform.h'),
-            os.path.join(_lib.INCLUDE, 'qd_hip.h'),
-            os.path.abspath(__file__)]
+    device_assembly): every header under csrc/ -- a new one can never be missing -- the public header and this file."""
+    return ([os.path.join(_lib.CSRC, f) for f in sorted(os.listdir(_lib.CSRC)) if f.endswith('.h')]
+            + [os.path.join(_lib.INCLUDE, 'qd_hip.h'), os.path.abspath(__file__)])
 
 
 def _tmp(path):

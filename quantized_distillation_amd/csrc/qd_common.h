@@ -17,6 +17,15 @@ typedef int64_t l2 __attribute__((ext_vector_type(2)));
 
 namespace qd {
 
+// Alignment the 16-byte (float4) global accesses of the single-tensor entry points need from their fp32 data pointers:
+// FOUR bytes.  global_load / global_store_dwordx4 take any dword-aligned address (the HSA queues run in unaligned access
+// mode), and a wave's 1 KiB per instruction covers the same lines either way: a tensor view that starts 4, 8 or 12 bytes
+// into a 16-byte granule runs at the speed of an aligned one (bucket 256, 64 Mi elements: 87.3 us against 85.3 us; 214 us
+// on the scalar two-pass kernels that the 16-byte requirement of round 1 sent it to).  tests/test_hip_parity.py::
+// test_views_at_every_4_byte_offset runs every entry point on such views.  (int64 index outputs and the workspace keep their
+// 16-byte requirement; the multi-tensor tables are built from 256-byte-aligned slots anyway.)
+constexpr uintptr_t kDataAlign = 3;
+
 // ---- explicitly global (address space 1) accesses ----
 // Pointers that a kernel reads out of a descriptor table in memory are generic to the compiler and
 // become flat_load / flat_store (which also occupy the LDS counter); these casts make them global_*.

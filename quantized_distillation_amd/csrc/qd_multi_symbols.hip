@@ -50,7 +50,7 @@ __device__ __forceinline__ float sym_level(float v, float a, float b, float sm1,
     const float t = u * sm1;
     return rintf(t);
 }
-// ... as the byte store_side1<MODE_QDQ> stores (qd_transform.h): (uint8_t)(int)level -- v_cvt_i32_f32, a NaN level is 0
+// ... as the byte store_side1<MODE_QDQ> stores (qd_element.h): (uint8_t)(int)level -- v_cvt_i32_f32, a NaN level is 0
 __device__ __forceinline__ uint32_t sym_byte(float level) { return (uint32_t)(uint8_t)(int)level; }
 
 // four levels of one float4 at sym + e: one 4-byte store (s4: sym + e is 4-byte aligned) or four 1-byte stores, the same bytes
@@ -101,7 +101,7 @@ __device__ __forceinline__ void sym_reg_row(const float* x, uint8_t* sym, int64_
 }
 
 // ---- LANES lanes (16: a DPP row, 64: the wave) and one arbitrary bucket [lo, hi): element by element, two passes (the second
-// is served by L1 / L2).  The reduction of bucket_lanes (qd_transform.h): fminf / fmaxf and a NaN flag.
+// is served by L1 / L2).  The reduction of bucket_lanes (qd_element.h): fminf / fmaxf and a NaN flag.
 template <int LANES>
 __device__ __forceinline__ void sym_lanes(const float* x, uint8_t* sym, int64_t lo, int64_t hi, int64_t bkt, int l, float sm1,
                                           float* alpha, float* beta) {

@@ -1,5 +1,5 @@
 // qd_multi_uniform.h -- the bodies the kernels of qd_multi_uniform.hip and qd_multi_uniform_out16.hip are instantiations of, and
-// what their entry points share on the host.  Private to those two files (qd_multi.h stays free of qd_transform.h).
+// what their entry points share on the host.  Private to those two files (qd_multi.h stays free of qd_element.h).
 //
 //   device   qdq4              four components through qdq / qdq_tab / qdq_stochastic / qdq_stochastic_tab: the ONE place that picks
 //            reg_row           a full bucket row in registers: load, clamp, min / max, alpha / beta, division split, quantize, store
@@ -17,7 +17,8 @@
 #include <initializer_list>
 #include <type_traits>
 
-#include "qd_transform.h"      // bucket_row16, KParams, Prep, transform<MODE_QDQ>; launch geometry
+#include "qd_element.h"        // bucket_lanes, KParams, Prep, transform<MODE_QDQ>
+#include "qd_launch.h"         // launch geometry
 #include "qd_multi.h"
 
 namespace {
@@ -104,7 +105,7 @@ __device__ __forceinline__ void reg_row(const float* x, O* out, int64_t lo, int 
     if (fdiv) body(std::true_type{}); else body(std::false_type{});
 }
 
-// The KParams of the row paths (bucket_row16, bucket_lanes*, bucket_row16_o16): tensor d in rows of `row`, nb of them.  The
+// The KParams of the row paths (bucket_lanes, bucket_lanes4, bucket_row16_o16): tensor d in rows of `row`, nb of them.  The
 // 16-bit row path stores through its own pointer.
 template <typename O>
 __device__ __forceinline__ KParams row_params(const QdTensorDesc& d, int64_t row, int64_t nb, float me, float sm1, int stochastic,
@@ -119,7 +120,7 @@ __device__ __forceinline__ KParams row_params(const QdTensorDesc& d, int64_t row
     return p;
 }
 
-// bucket_lanes<MODE_QDQ, 16> (qd_transform.h) with a 16-bit store: a DPP row processes one arbitrary bucket [lo, hi) with scalar
+// bucket_lanes<MODE_QDQ, 16> (qd_element.h) with a 16-bit store: a DPP row processes one arbitrary bucket [lo, hi) with scalar
 // accesses in two passes -- the ragged last bucket, short buckets, odd bucket sizes, pointers that the register path does not
 // take.  The same reduction, the same transform<MODE_QDQ>; q needs 2-byte alignment only.  No alpha / beta / level outputs: the
 // multi-tensor launches have none.
@@ -170,7 +171,7 @@ __device__ __forceinline__ Levels levels_of(float sm1, int lane) {
 
 // ---- bucketed, one bucket size for the launch: tile t of tensor d in k_multi_uniform, _opt, _lv and _o16 ----
 // A tile = 4 buckets of one tensor = one wave iteration; a DPP row owns a bucket.  Full ROW-element buckets of a tensor that is
-// vector_aligned take reg_row, everything else the row path (bucket_row16; 16 bits: bucket_row16_o16).  Both give the same bits.
+// vector_aligned take reg_row, everything else the row path (bucket_lanes<16>; 16 bits: bucket_row16_o16).  Both give the same bits.
 template <int ROW, bool CLAMP, int STOCH, typename O>
 __device__ __forceinline__ void bucketed_tile(const QdTensorDesc d, int64_t t, int64_t bucket, const Levels& lv, float me,
                                               uint64_t seed_t) {
@@ -189,7 +190,7 @@ __device__ __forceinline__ void bucketed_tile(const QdTensorDesc d, int64_t t, i
     if (fast) {
         reg_row<(ROW > 0 ? ROW / 64 : 1), CLAMP, STOCH>(p.x, (O*)d.q, lo, l, pp, lv.sm1, lv.use_tab, lv.tab, seed_t);
     } else {
-        if constexpr (std::is_same<O, float>::value) bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
+        if constexpr (std::is_same<O, float>::value) bucket_lanes<MODE_QDQ, 16>(p, nullptr, bkt, lo, hi, l, pp);
         else bucket_row16_o16<O>(p, (O*)d.q, lo, hi, l, pp);
     }
 }

@@ -18,10 +18,16 @@
 // Every kernel here is an instantiation of a body of qd_multi_uniform.h; the kernels stay separate symbols, so a launch without
 // options runs code that has never heard of them:
 //   k_multi_uniform, _opt, _lv   bucketed_tile<ROW, CLAMP, STOCH, float>, the level count an argument (the first two) or levels[ti]
-//   k_multi_uniform_bk           its own tile rule (bucket_tiles, qd_multi.h) around reg_row and the row paths of qd_transform.h
+//   k_multi_uniform_bk           its own tile rule (bucket_tiles, qd_multi.h) around reg_row and the row paths of qd_element.h
 //   k_mg_minmax, _opt            mg_minmax_tile<CLAMP>
 //   k_mg_apply, _opt, _lv        mg_apply_tile<CLAMP, STOCH, float>
 #include "qd_multi_uniform.h"
+// Nothing of this header is used here.  It stays because of k_mg_fold: the compiler assigns two scalar registers of its
+// block_minmax loop the other way round (same instructions, same size) unless an earlier kernel of the unit has inlined
+// block_minmax already, and until now k_minmax_partial / k_minmax_final of this header were those kernels.  The unit
+// therefore still emits the two (4 KB, never launched from here); dropping them changes k_mg_fold's bytes -- a later
+// change, with an A/B measurement.  (qd_multi_uniform_out16.hip has no such kernel and does without.)
+#include "qd_single_kernels.h"
 
 namespace {
 
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void k_mg_apply_lv(const QdTensorDesc* __restr
 // another tensor.  Which body a bucket takes:
 //   row <= 256, a DPP row per bucket: a full row of a 16-byte aligned tensor takes reg_row at row 64 / 128 / 256 (a scalar
 //     branch on the row, the wave is uniform in it), bucket_lanes4<16> at any other multiple of 4; a ragged last row, a row that
-//     is no multiple of 4 and an unaligned tensor take bucket_row16;
+//     is no multiple of 4 and an unaligned tensor take bucket_lanes<16>;
 //   row > 256, the wave per bucket: bucket_lanes4<64> for a full row that is a multiple of 4 in an aligned tensor, else
 //     bucket_lanes<64>.  Two passes, the second served by L2.  A row of more than 64 Ki elements (a bucket size beyond the
 //     tensor included) still runs on that one wave: correct, not tuned -- whole-tensor scaling has the bucket_size=None launch.
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(256) void k_multi_uniform_bk(const QdTensorDesc* __
                 else if (p.row == 64) reg_row<1, true, STOCH>(p.x, p.out, lo, l, pp, lv.sm1, lv.use_tab, lv.tab, seed_t);
                 else bucket_lanes4<MODE_QDQ, 16>(p, nullptr, bkt, lo, l, pp);
             } else {
-                bucket_row16<MODE_QDQ>(p, nullptr, bkt, lo, hi, l, pp);
+                bucket_lanes<MODE_QDQ, 16>(p, nullptr, bkt, lo, hi, l, pp);
             }
         }
     }

@@ -10,7 +10,7 @@ namespace {
 // reduction (k_bucket_chunk(_any): a chunk staged in registers / LDS, three phases per chunk, 2-6 waves per SIMD; at
 // bucket 33 / 250 the call ran at 132 / 125 us, 57-61 % of the HBM peak, at 64 / 256 points 210-295 us).  Here every lane
 // simply takes float4s of u in memory order -- a contiguous 4 KiB tile per wave, kStreamU float4s per lane in flight -- assigns the four elements (joint search up to 32
-// points, the 2048-cell table above that: qd_transform.h), and rescales each with the (alpha, beta) of ITS bucket: the
+// points, the 2048-cell table above that: qd_points.h), and rescales each with the (alpha, beta) of ITS bucket: the
 // float4's first element lies in bucket b0 = e / row (one 32-bit division per lane and tile, then advanced by 256 elements), the others in
 // b0 or b0 + 1 -- two loads per array, served by L1 / L2 as neighbouring lanes ask for the same buckets.  One coalesced
 // 16-byte load and store per float4, indices as one uint32 (uint8) or two 16-byte stores (int64, exchanged inside the DPP

@@ -29,7 +29,7 @@ constexpr int kMaxPoints = 1024;        // LDS table of quantization points
 constexpr int kPartialBlocks = 1024;    // stage-1 blocks of every two-stage reduction
 constexpr int kCells = 256;             // uniform grid over [0,1] that narrows the midpoint search (k > 32)
 constexpr int kSmallTable = 32;
-constexpr int kFineCells = 2048;        // the fine cell table (PointStore, qd_transform.h)
+constexpr int kFineCells = 2048;        // the fine cell table (PointStore, qd_points.h)
 // Grid cap of the kernels that build the fine table, in blocks per CU (6 are resident next to 26.6 KB of LDS).  Measured, K5
 // k = 256 at bucket 256 / 1000, 64 Mi elements (round 2's narrowed search: 117 / 144 us): 6 -> 102 / 110 us (every resident
 // block builds its table at the same moment, nothing to overlap it with), 12 -> 98 / 105, 24 -> 95 / 102, 48 -> 101 / 111,

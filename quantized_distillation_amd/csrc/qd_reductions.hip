@@ -4,7 +4,8 @@
 //       qd_bucket_argminmax_f32  idx_min_rows / idx_max_rows                  :85-90,103-104
 //   K6  qd_point_grad_f32        nonUniformQuantization_variable.backward     :471-506
 // Its own translation unit so that hipcc builds it next to qd_kernels.hip / qd_nearest.hip / qd_scale.hip (parallel build).
-#include "qd_transform.h"      // shared helpers: workspace carving, launch geometry
+#include "qd_launch.h"         // shared helpers: workspace carving, launch geometry
+#include "../../include/qd_hip.h"
 
 namespace {
 
@@ -733,7 +734,7 @@ int qd_point_grad_f32(const float* g, const void* idx, int idx_bytes, const floa
         const bool big = lds_bytes > 16 * 1024;
         if (big) {
             const int per_cu = (int)((160 * 1024) / lds_bytes) > 0 ? (int)((160 * 1024) / lds_bytes) : 1;
-            const int resident = num_cus() * per_cu;
+            const int resident = device_cus() * per_cu;
             if (blocks > resident) blocks = resident;
         }
 #define QD_PG(KR, IDXB, BK, U, MG, ...)                                                                             \
@@ -754,7 +755,7 @@ int qd_point_grad_f32(const float* g, const void* idx, int idx_bytes, const floa
                 const size_t tl = (size_t)k * 64 * sizeof(float);                                                   \
                 int per_cu_t = (int)((160 * 1024) / (tl + 64));   /* LDS; the 142-163 VGPRs allow 3 blocks per CU */  \
                 if (per_cu_t > kTurnsBlocksPerCu) per_cu_t = kTurnsBlocksPerCu;                                      \
-                int tb = num_cus() * per_cu_t;                                                                       \
+                int tb = device_cus() * per_cu_t;                                                                       \
                 if (tb > blocks_all) tb = blocks_all;                                                                \
                 if (tb > (int)max_rows) tb = (int)max_rows;                                                          \
                 if (tb < 1) tb = 1;                                                                                  \
@@ -781,7 +782,7 @@ int qd_point_grad_f32(const float* g, const void* idx, int idx_bytes, const floa
         const size_t lds_bytes = (size_t)k * C * sizeof(float);
         int want = blocks_for(n, threads * 4 * 4);
         const int per_cu = (int)((160 * 1024) / (lds_bytes + 256));
-        const int resident = num_cus() * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
+        const int resident = device_cus() * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
         if (want > resident) want = resident;
         if (want > max_rows) want = (int)max_rows;
         blocks = want < 1 ? 1 : want;

@@ -7,7 +7,8 @@
 //       qd_multi_ste_in16_plan, qd_multi_ste_backward_in16_f32   the same reading fp16 / bf16 gradients (k_multi_ste_in16)
 //       qd_multi_ste_buckets_plan, qd_multi_ste_backward_buckets_f32   a level count and a bucket size per tensor (k_multi_ste_bk)
 // Its own translation unit: K7, K7m and K8 are the only users of ste_cut and of the two K7 bodies.
-#include "qd_transform.h"      // shared helpers: workspace carving, launch geometry
+#include "qd_launch.h"         // shared helpers: workspace carving, launch geometry
+#include "../../include/qd_hip.h"
 #include "qd_multi.h"          // owner_of, fill_prefix for K7m
 
 namespace {

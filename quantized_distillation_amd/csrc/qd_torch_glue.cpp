@@ -201,7 +201,7 @@ PyObject* glue_uniform(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
 // pair therefore comes from a tensor of the call's own (the [2, nb, 1] / [2, 1] branch of requests above a quarter
 // slab): allocated from the graph's private pool, read through _ab -- no copy on first read, so a kept ScalingFunction
 // shows the pair of the latest replay, as one from the general path does -- and g_slabs is left as the eager calls left
-// it.  The query is one hipStreamIsCapturing per call, the form stream_capturing (qd_transform.h) already uses.
+// it.  The query is one hipStreamIsCapturing per call, the form stream_capturing (qd_launch.h) already uses.
 PyTypeObject* g_sf_type = nullptr;
 PyObject *s_bucket_size, *s_n, *s_ab, *s_ab_slab, *s_ab_off, *s_arg_source, *s_arg_version, *s_mean_tensor, *s_zero;
 

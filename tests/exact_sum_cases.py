@@ -212,7 +212,7 @@ def pg_expected(case):
 
 def pg_path(k, idx_bytes, n, bucket, g_phase=0, idx_phase=0):
     """Which kernel qd_point_grad_f32 reaches and the threads of its blocks -- the dispatcher's conditions restated.  The fp32
-    data needs FOUR-byte alignment only (kDataAlign = 3, csrc/qd_transform.h: 16-byte loads take any dword-aligned address), so
+    data needs FOUR-byte alignment only (kDataAlign = 3, csrc/qd_common.h: 16-byte loads take any dword-aligned address), so
     g at +4 bytes stays on the fast kernels; the indices need their own 16 (int64) or 4 (uint8) bytes."""
     nb, row = geometry(max(n, 1), bucket)
     pow2 = nb == 1 or (row & (row - 1)) == 0

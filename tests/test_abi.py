@@ -228,7 +228,7 @@ def test_write_once_outputs_keep_their_non_temporal_hint(lib):
     optimiser can lose it: when it merges two copies of a loop the merged store drops !nontemporal, and the kernel then
     runs with plain stores (scale_down shipped like that through round 3: 92 us against 85 us at bucket 256).  Read from
     the disassembly of the shipped code objects: every 16-byte global store of every kernel carries `nt`, except the int64
-    point indices of the nearest-point kernels (plain on purpose: 175.8 us against 180.0 us with the hint, qd_transform.h
+    point indices of the nearest-point kernels (plain on purpose: 175.8 us against 180.0 us with the hint, qd_element.h
     store_side4_row) and the two in-place epilogues that rewrite only the float4s they change."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, 'tools'))

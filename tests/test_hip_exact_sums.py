@@ -210,7 +210,7 @@ def test_ste_bucket_sums_bit_for_bit(lib, shape):
     """The WHOLE output: g everywhere, g + S and g - S at the two touched places of every bucket, S with one possible value.
     The register tiles (rows 64 .. 1024) with the ragged last bucket behind them in ste_wave_bucket, ste_wave_bucket for every
     other row; phase 4: the same kernels with x, g and out 4 bytes into a 16-byte granule (fp32 data needs four-byte alignment
-    only, csrc/qd_transform.h: kDataAlign).  x times 2^-104 takes the IEEE division (exact_sum_cases.STE_SCALES)."""
+    only, csrc/qd_common.h: kDataAlign).  x times 2^-104 takes the IEEE division (exact_sum_cases.STE_SCALES)."""
     bucket, nfull, tail, what = shape
     if what == 'vec':
         bpw = 4 if bucket <= 256 else 1

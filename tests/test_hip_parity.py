@@ -655,7 +655,7 @@ def test_point_gradient_long_streams_at_any_bucket_size(bucket, k):
 @pytest.mark.parametrize('k', [33, 64, 65, 200, 256, 1000])
 def test_fine_cell_table_with_crowded_and_degenerate_points(k):
     """Above 32 points the pre-processed forward (midpoint rule) answers an element from a 2048-cell table when its cell holds
-    at most one midpoint and searches inside the cell otherwise (qd_transform.h).  Point sets that stress exactly that:
+    at most one midpoint and searches inside the cell otherwise (qd_points.h).  Point sets that stress exactly that:
     all points inside ONE cell, a bell-shaped crowd (what a percentile initialisation produces), duplicates, points ON cell
     boundaries j / 2048, points outside [0, 1]; values on boundaries, on midpoints, below 0, above 1, +-inf and NaN.  Every
     call here is pre-scaled, so what qd_transform_plan names for it is k_nearest_prescaled_stream (every bucket size with more
@@ -1452,7 +1452,7 @@ def test_quantize_bit_exact_at_extreme_scales(bucket):
 def test_scale_down_bit_exact_at_extreme_scales(bucket):
     """scale_down RETURNS u = (x - beta) / alpha, so where its vector kernel divides through y = RN(1/alpha) and two FMAs
     (buckets whose alpha is in [2^-60, 2^100] and whose nonzero numerators are all >= max(2^-100, alpha 2^-120): a normal
-    quotient; qd_transform.h scale_fast_ok) every BIT of u must equal the IEEE quotient of quant_functions.py:106-107.
+    quotient; qd_bucket_vec_kernels.h vec_bucket, qd_common.h scale_fast_ok) every BIT of u must equal the IEEE quotient of quant_functions.py:106-107.
     Buckets on both sides of each condition: numerators below 2^-100, denormal quotients (where the shortcut can differ in
     the last bit and must not be taken), quotients at the 2^-120 threshold, tiny / huge / mixed scales, zeros next to
     denormals, constant buckets -- u, alpha, beta compared as bit patterns with the numpy oracle."""

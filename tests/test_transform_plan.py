@@ -6,7 +6,7 @@ bucket size 1 .. 40000 in the three modes, at four tensor lengths each (many buc
 2, one bucket + 1), with the pointers aligned and not, the side outputs asked for and not, and 4 / 33 / 65 / 256 points:
 
   * the capacity contracts the kernels index their LDS, registers and the tensor by (stated next to the kernel lines they
-    protect in qd_transform.h): a launcher slip there is an out-of-bounds access on the device;
+    protect in qd_bucket_vec_kernels.h and qd_bucket_row_kernels.h): a launcher slip there is an out-of-bounds access on the device;
   * the boundaries between the kernel families, and the thresholds of the single-bucket path;
   * agreement with the shipped library: every name the plan returns is a kernel of libqd_hip.so, and every shipped
     instantiation of the transform kernels is planned for some input -- a stranded instantiation fails here;
@@ -83,7 +83,7 @@ def sweep_lengths(buckets):
 
 
 def table_bytes(k, fine):
-    """The point table at the start of a nearest-point kernel's dynamic LDS (PointStore, qd_transform.h)."""
+    """The point table at the start of a nearest-point kernel's dynamic LDS (PointStore, qd_points.h)."""
     coarse = 2 * 1024 * 4 + 2 * (256 + 4) * 4
     return np.where(k <= 32, 2 * 32 * 4, coarse + np.where(fine != 0, 2048 * 8, 0))
 

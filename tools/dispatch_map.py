@@ -2,7 +2,8 @@
 """Which kernel does each kind of call reach?  (mode, bucket-size class, point count, alignment, tensor size) -> kernel(s).
 
 The launchers of csrc/qd_transform.h / qd_reductions.hip / qd_ste.hip / qd_multi_uniform.hip / qd_multi_dq.hip / qd_codec.hip pick an
-instantiation from the call's geometry.
+instantiation from the call's geometry (qd_transform.h holds the launcher; its kernels: qd_bucket_vec_kernels.h,
+qd_bucket_row_kernels.h, qd_single_kernels.h).
 This tool makes that choice visible: it issues a labelled list of calls with a MARKER kernel between them (a tiny
 torch.bitwise_xor, which nothing else here launches), under `rocprofv3 --kernel-trace`, and cuts the dispatch sequence at
 the markers.

@@ -16,7 +16,8 @@ tests/test_launch_coverage.py asserts --check on the committed profiles/r06_laun
 adds an instantiation fails the CPU suite until the coverage run has been repeated.
 
 Kernels are matched by their demangled name without the argument list.  The same template can be instantiated in several
-translation units (everything sits in anonymous namespaces: qd_transform.h is included four times); a name counts as
+translation units (everything sits in anonymous namespaces: qd_transform.h and the kernel headers under it are included by
+three units, qd_element.h and qd_single_kernels.h by more); a name counts as
 launched whichever unit's copy ran.
 """
 import csv
