@@ -160,7 +160,30 @@ def build_host(force=False, verbose=False):
     return out
 
 
+INFER_SOURCES = ['qdi_layers.hip']                  # csrc/infer/: libqd_infer.so (include/qd_infer.h), nothing of it in SOURCES
+
+
+def build_infer(force=False, verbose=False):
+    """libqd_infer.so next to libqd_hip.so: Linear and Embedding from packed weights (csrc/infer/, include/qd_infer.h).  The
+    flags of build_extension (the weight value needs the same correctly rounded division and no contraction), the same
+    stale check against every header, and an atomic replace of a complete file."""
+    from . import _infer
+    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_SOURCES]
+    out = _infer.LIB_PATH
+    deps = srcs + _headers() + [os.path.join(_lib.INCLUDE, 'qd_infer.h')]
+    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
+        return out
+    tmp = _tmp(out)
+    cmd = [hipcc()] + HIPCC_FLAGS + ['-I', _lib.INCLUDE] + srcs + ['-o', tmp]
+    if verbose:
+        print(' '.join(cmd))
+    subprocess.check_call(cmd)
+    os.replace(tmp, out)
+    return out
+
+
 if __name__ == '__main__':
     print(build_extension(force=True, verbose=True))
+    print(build_infer(force=True, verbose=True))
     print(build_glue(force=True, verbose=True))
     print(build_host(force=True, verbose=True))
