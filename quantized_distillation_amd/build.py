@@ -169,12 +169,19 @@ def build_infer(force=False, verbose=False):
     stale check against every header, and an atomic replace of a complete file."""
     from . import _infer
     srcs = [os.path.join(_infer.CSRC, f) for f in INFER_SOURCES]
-    out = _infer.LIB_PATH
-    deps = srcs + _headers() + [os.path.join(_lib.INCLUDE, 'qd_infer.h')]
+    return _build_infer_library(srcs, _infer.LIB_PATH, 'qd_infer.h', HIPCC_FLAGS, force, verbose)
+
+
+def _build_infer_library(srcs, out, header, flags, force, verbose):
+    """One hipcc call from sources under csrc/infer/ to a library; stale against the sources, every header under csrc/ and
+    csrc/infer/, the public header and this file."""
+    from . import _infer
+    deps = (srcs + _headers() + [os.path.join(_infer.CSRC, f) for f in sorted(os.listdir(_infer.CSRC)) if f.endswith('.h')]
+            + [os.path.join(_lib.INCLUDE, header)])
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
         return out
     tmp = _tmp(out)
-    cmd = [hipcc()] + HIPCC_FLAGS + ['-I', _lib.INCLUDE] + srcs + ['-o', tmp]
+    cmd = [hipcc()] + flags + ['-I', _lib.INCLUDE] + srcs + ['-o', tmp]
     if verbose:
         print(' '.join(cmd))
     subprocess.check_call(cmd)
@@ -182,8 +189,25 @@ def build_infer(force=False, verbose=False):
     return out
 
 
+INFER_MM_SOURCES = ['qdm_linear.hip']               # csrc/infer/: libqd_infer_mm.so (include/qd_infer_mm.h), nothing of it in SOURCES or INFER_SOURCES
+# HIPCC_FLAGS, and the packed-fp32 VALU forms (v_pk_add / mul / fma_f32) switched off for the device code of this library: its
+# arithmetic is MFMA plus ONE fp32 addition per output (the bias), which is to stay one scalar v_add_f32 per element, as the
+# header words it.  Nothing is lost: there is no other fp32 VALU arithmetic on the hot path.
+INFER_MM_FLAGS = HIPCC_FLAGS + ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
+
+
+def build_infer_mm(force=False, verbose=False):
+    """libqd_infer_mm.so next to libqd_infer.so: the batched Linear layer from packed weights on fp32 MFMA (csrc/infer/
+    qdm_linear.hip, include/qd_infer_mm.h).  HIPCC_FLAGS (the same weight value: correctly rounded division, no contraction),
+    the stale check and the atomic replace of build_infer."""
+    from . import _infer, _infer_mm
+    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_MM_SOURCES]
+    return _build_infer_library(srcs, _infer_mm.LIB_PATH, 'qd_infer_mm.h', INFER_MM_FLAGS, force, verbose)
+
+
 if __name__ == '__main__':
     print(build_extension(force=True, verbose=True))
     print(build_infer(force=True, verbose=True))
+    print(build_infer_mm(force=True, verbose=True))
     print(build_glue(force=True, verbose=True))
     print(build_host(force=True, verbose=True))

@@ -11,7 +11,7 @@
 // division the codec uses (qd_codec.hip: k_unpack_any), so a weight is bit for bit what qd_unpack_uniform_f32 writes and
 // no lane divides per element.  The bucket of an element is found with one division per lane and row (linear) or per
 // group of four (embedding); inside a group an element that leaves the group's first bucket steps on (three buckets at the most).
-#include "../qd_common.h"
+#include "qdi_packed.h"       // Packed, describe, stream_bits, divmod, build_quotients, decode4: shared with qdm_linear.hip
 
 #include "../../../include/qd_infer.h"
 
@@ -19,75 +19,12 @@ using namespace qd;
 
 namespace {
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));     // a 16-byte access at the 4-byte alignment of fp32 data
-
 int g_grid_cap = 0;                                                    // qdi_set_grid_cap: 0 = none
 
 int capped(int64_t blocks, int64_t own_cap) {
     if (blocks > own_cap) blocks = own_cap;
     if (g_grid_cap >= 1 && blocks > g_grid_cap) blocks = g_grid_cap;
     return blocks < 1 ? 1 : (int)blocks;
-}
-
-// By-value description of the packed weight, shared by both kernels.
-struct Packed {
-    const uint8_t* packed;
-    const float* alpha;
-    const float* beta;
-    int64_t rows, cols;
-    int64_t nbytes;          // of the stream: ceil(rows cols bits / 8)
-    int64_t bucket;          // EFFECTIVE bucket: rows cols where the tensor is one bucket, so e / bucket is the bucket of e
-    int levels, bits;
-    int small;               // rows cols < 2^32: 32-bit divisions
-};
-
-// The 32 stream bits from bit p on (a group of four level indices is 4 bits <= 32 bits of them): two aligned 32-bit words
-// and a shift where both lie wholly inside the stream, byte by byte (five at the most) at its end -- group_bits of
-// qd_codec.hip for every width.
-__device__ __forceinline__ uint32_t stream_bits(const uint8_t* packed, int64_t p, int64_t nbytes) {
-    const int64_t w = p >> 5;
-    if ((w + 2) * 4 <= nbytes) {
-        const uint32_t lo = ((const uint32_t*)packed)[w], hi = ((const uint32_t*)packed)[w + 1];
-        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (p & 31));
-    }
-    uint64_t acc = 0;
-    const int64_t b0 = p >> 3;
-    for (int c = 0; c < 5 && b0 + c < nbytes; ++c) acc |= (uint64_t)packed[b0 + c] << (8 * c);
-    return (uint32_t)(acc >> (p & 7));
-}
-
-__device__ __forceinline__ void divmod(int64_t a, int64_t b, int small, int64_t& q, int64_t& r) {
-    if (small) { q = (uint32_t)a / (uint32_t)b; } else { q = a / b; }
-    r = a - q * b;
-}
-
-// The `levels` quotients c / (levels - 1), each the correctly rounded fp32 division of k_unpack_any.
-__device__ __forceinline__ void build_quotients(float* qtab, int levels) {
-    const float sm1 = (float)(levels - 1);
-    for (int c = threadIdx.x; c < levels; c += blockDim.x) qtab[c] = (float)c / sm1;
-    __syncthreads();
-}
-
-// The nv <= 4 weights of the group whose first element is e (bucket bkt, rem elements into it): w[c] for c < nv.
-__device__ __forceinline__ void decode4(const Packed& P, const float* qtab, int64_t e, int64_t bkt, int64_t rem, int nv, float (&w)[4]) {
-    const uint32_t code = stream_bits(P.packed, e * P.bits, P.nbytes);
-    const uint32_t mask = (1u << P.bits) - 1u;
-    const float a0 = P.alpha[bkt], b0 = P.beta[bkt];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        w[c] = 0.0f;
-        if (c < nv) {
-            float a = a0, b = b0;
-            if (rem + c >= P.bucket) {                                   // the group leaves its first bucket (bucket < 4: more than once)
-                int64_t bc = bkt, rr = rem + c;
-                do { rr -= P.bucket; ++bc; } while (rr >= P.bucket);     // rem < bucket and c <= 3: three steps at the most
-                a = P.alpha[bc]; b = P.beta[bc];
-            }
-            float v = qtab[(code >> (c * P.bits)) & mask] * a;          // the three operations after the division, each rounded
-            v = v + b;
-            w[c] = v + 0.0f;
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void k_embedding(Packed P, const int64_t* idx, int64_t count, float* out) {
@@ -179,21 +116,6 @@ __global__ __launch_bounds__(256) void k_linear(Packed P, const float* x, int64_
             }
         }
     }
-}
-
-bool describe(Packed& P, const uint8_t* packed, const float* alpha, const float* beta, int64_t rows, int64_t cols, int64_t bucket,
-              int levels, int bits) {
-    if (rows < 0 || cols < 0 || bucket < 0 || levels < 2 || levels > 256 || bits < 1 || bits > 8 || levels > (1 << bits)) return false;
-    int64_t n = 0, nbits = 0;
-    if (__builtin_mul_overflow(rows, cols, &n) || __builtin_mul_overflow(n, (int64_t)bits, &nbits) || nbits > INT64_MAX - 64) return false;
-    if ((((uintptr_t)packed) & 3) || (((uintptr_t)alpha) & 3) || (((uintptr_t)beta) & 3)) return false;
-    P.packed = packed; P.alpha = alpha; P.beta = beta;
-    P.rows = rows; P.cols = cols;
-    P.nbytes = (nbits + 7) >> 3;
-    P.bucket = (bucket == 0 || n < bucket) ? (n > 0 ? n : 1) : bucket;
-    P.levels = levels; P.bits = bits;
-    P.small = n < ((int64_t)1 << 32);
-    return true;
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 """nn.Linear and nn.Embedding that run straight from the packed level indices of a quantized weight (libqd_infer.so,
-include/qd_infer.h): a layer keeps `bits` bits per weight + (alpha, beta) per bucket on the device and never holds the
+include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h): a layer keeps `bits` bits per weight + (alpha, beta) per bucket on the device and never holds the
 fp32 tensor.  The format is codec.pack_uniform's for the 2-D weight; the value of a weight is bit for bit what
 PackedUniform.unpack() gives.
 
@@ -107,16 +107,37 @@ def _pack_weight(weight, s, bucket_size, bits, what):
     return codec.pack_uniform(weight.detach(), s, bucket_size, bits)
 
 
+def _batched_from(value):
+    if value is not None and (not isinstance(value, int) or isinstance(value, bool) or value < 1):
+        raise ValueError('batched_from must be None or an integer >= 1 (the number of rows of x from which calls take the '
+                         'batched MFMA kernel), got %r' % (value,))
+    return value
+
+
 class PackedLinear(_PackedModule):
-    """y = x W^T + bias with W[N, K] read from its packed level indices (qdi_linear_packed_f32)."""
+    """y = x W^T + bias with W[N, K] read from its packed level indices.
+
+    batched_from=None: every call is qdi_linear_packed_f32 (libqd_infer.so: one wave per output row, made for a handful of rows
+    of x).  batched_from=M0: calls with at least M0 rows of x (the product of x's leading dimensions) are
+    qdm_linear_packed_f32 (libqd_infer_mm.so, loaded on first use: fp32 MFMA, the weights decoded once per 64 rows of x).  Both
+    keep the bound of include/qd_infer.h; their summation orders differ, so their results differ in the last bits."""
+
+    def __init__(self, packed, bias=None, batched_from=None):
+        batched_from = _batched_from(batched_from)
+        super().__init__(packed, bias)
+        self.batched_from = batched_from
 
     @classmethod
-    def from_linear(cls, linear, s, bucket_size=256, bits=None):
+    def from_linear(cls, linear, s, bucket_size=256, bits=None, batched_from=None):
         """Quantize the weight of an nn.Linear with `s` levels per bucket; bits=None takes codec.min_bits_for_levels(s)."""
         if not isinstance(linear, nn.Linear):
             raise TypeError('from_linear takes an nn.Linear, got %r' % type(linear))
+        batched_from = _batched_from(batched_from)
         pk = _pack_weight(linear.weight, s, bucket_size, bits, 'PackedLinear.from_linear')
-        return cls(pk, None if linear.bias is None else linear.bias.detach().clone())
+        return cls(pk, None if linear.bias is None else linear.bias.detach().clone(), batched_from)
+
+    def extra_repr(self):
+        return super().extra_repr() + ', batched_from=%r' % (self.batched_from,)
 
     @property
     def in_features(self):
@@ -146,9 +167,12 @@ class PackedLinear(_PackedModule):
         xc = x.detach().contiguous()
         m = int(torch.Size(x.shape[:-1]).numel())
         y = torch.empty(tuple(x.shape[:-1]) + (self.rows,), dtype=torch.float32, device=x.device)
-        _infer.check(_infer.load().qdi_linear_packed_f32(*self._format_args(), xc.data_ptr(), m,
-                                                         None if self.bias is None else self.bias.data_ptr(), y.data_ptr(),
-                                                         _lib.stream_ptr()))
+        args = self._format_args() + (xc.data_ptr(), m, None if self.bias is None else self.bias.data_ptr(), y.data_ptr(), _lib.stream_ptr())
+        if self.batched_from is not None and m >= self.batched_from:
+            from . import _infer_mm                                       # libqd_infer_mm.so: on first use only
+            _infer_mm.check(_infer_mm.load().qdm_linear_packed_f32(*args))
+        else:
+            _infer.check(_infer.load().qdi_linear_packed_f32(*args))
         return y
 
     def unpack(self):
@@ -212,10 +236,11 @@ class PackedEmbedding(_PackedModule):
         return emb
 
 
-def pack_modules(model, s, bucket_size=256, bits=None, skip=()):
+def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=None):
     """Replace every nn.Linear and nn.Embedding of `model` in place by its packed form.  skip: names (model.named_modules())
-    left as they are; s: the level count, or a mapping from module name to it (every replaced module must be in it).
-    Returns {name: (fp32_bytes, packed_bytes)} of what was replaced."""
+    left as they are; s: the level count, or a mapping from module name to it (every replaced module must be in it);
+    batched_from: PackedLinear's, for every Linear replaced.  Returns {name: (fp32_bytes, packed_bytes)} of what was replaced."""
+    batched_from = _batched_from(batched_from)
     skip = set(skip)
     todo = [(name, mod) for name, mod in model.named_modules() if isinstance(mod, (nn.Linear, nn.Embedding)) and name not in skip]
     unknown = skip - {name for name, _ in model.named_modules()}
@@ -231,7 +256,10 @@ def pack_modules(model, s, bucket_size=256, bits=None, skip=()):
     for name, mod, (s_i, bits_i) in plan:
         if name == '':
             raise ValueError('the model itself is an nn.Linear / nn.Embedding: use from_linear / from_embedding')
-        new = (PackedLinear.from_linear if isinstance(mod, nn.Linear) else PackedEmbedding.from_embedding)(mod, s_i, bucket_size, bits_i)
+        if isinstance(mod, nn.Linear):
+            new = PackedLinear.from_linear(mod, s_i, bucket_size, bits_i, batched_from)
+        else:
+            new = PackedEmbedding.from_embedding(mod, s_i, bucket_size, bits_i)
         parent_name, _, leaf = name.rpartition('.')
         parent = model.get_submodule(parent_name) if parent_name else model
         setattr(parent, leaf, new)
