@@ -205,9 +205,21 @@ def build_infer_mm(force=False, verbose=False):
     return _build_infer_library(srcs, _infer_mm.LIB_PATH, 'qd_infer_mm.h', INFER_MM_FLAGS, force, verbose)
 
 
+INFER_CONV_SOURCES = ['qdc_conv2d.hip']             # csrc/infer/: libqd_infer_conv.so (include/qd_infer_conv.h), in no other source list
+
+
+def build_infer_conv(force=False, verbose=False):
+    """libqd_infer_conv.so next to libqd_infer_mm.so: nn.Conv2d from packed weights as an implicit GEMM on fp32 MFMA (csrc/infer/
+    qdc_conv2d.hip, include/qd_infer_conv.h).  INFER_MM_FLAGS: the one fp32 VALU addition per output is the bias here too."""
+    from . import _infer, _infer_conv
+    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_CONV_SOURCES]
+    return _build_infer_library(srcs, _infer_conv.LIB_PATH, 'qd_infer_conv.h', INFER_MM_FLAGS, force, verbose)
+
+
 if __name__ == '__main__':
     print(build_extension(force=True, verbose=True))
     print(build_infer(force=True, verbose=True))
     print(build_infer_mm(force=True, verbose=True))
+    print(build_infer_conv(force=True, verbose=True))
     print(build_glue(force=True, verbose=True))
     print(build_host(force=True, verbose=True))

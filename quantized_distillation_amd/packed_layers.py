@@ -1,10 +1,11 @@
-"""nn.Linear and nn.Embedding that run straight from the packed level indices of a quantized weight (libqd_infer.so,
-include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h): a layer keeps `bits` bits per weight + (alpha, beta) per bucket on the device and never holds the
+"""nn.Linear, nn.Embedding and nn.Conv2d that run straight from the packed level indices of a quantized weight (libqd_infer.so,
+include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h; convolutions libqd_infer_conv.so,
+include/qd_infer_conv.h): a layer keeps `bits` bits per weight + (alpha, beta) per bucket on the device and never holds the
 fp32 tensor.  The format is codec.pack_uniform's for the 2-D weight; the value of a weight is bit for bit what
 PackedUniform.unpack() gives.
 
 Inference only: the outputs carry no grad_fn.  To train or fine-tune, take `unpack()` -- an ordinary nn.Linear /
-nn.Embedding with the fake-quantized fp32 weights.  HIP device only: there is no CPU path.
+nn.Embedding / nn.Conv2d with the fake-quantized fp32 weights.  HIP device only: there is no CPU path.
 """
 import collections.abc
 
@@ -236,13 +237,101 @@ class PackedEmbedding(_PackedModule):
         return emb
 
 
-def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=None):
-    """Replace every nn.Linear and nn.Embedding of `model` in place by its packed form.  skip: names (model.named_modules())
-    left as they are; s: the level count, or a mapping from module name to it (every replaced module must be in it);
-    batched_from: PackedLinear's, for every Linear replaced.  Returns {name: (fp32_bytes, packed_bytes)} of what was replaced."""
+def _pair(value, what, least):
+    """An int or a pair of ints >= least, as (h, w)."""
+    pair = (value, value) if isinstance(value, int) else tuple(value) if isinstance(value, (tuple, list)) else None
+    if pair is None or len(pair) != 2 or any(not isinstance(v, int) or isinstance(v, bool) or v < least for v in pair):
+        raise ValueError('%s must be an integer >= %d or a pair of them, got %r' % (what, least, value))
+    return pair
+
+
+def _check_conv2d(conv, what):
+    """The nn.Conv2d that have a packed form: groups 1, dilation 1, zero padding given in numbers."""
+    if not isinstance(conv, nn.Conv2d):                                  # nn.ConvTranspose2d is no nn.Conv2d
+        raise ValueError('%s takes an nn.Conv2d (transposed convolutions have no packed form), got %r' % (what, type(conv)))
+    if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
+        raise ValueError('%s: groups = %d, dilation = %s: only groups 1 and dilation 1 have a packed form' % (what, conv.groups, tuple(conv.dilation)))
+    if conv.padding_mode != 'zeros' or isinstance(conv.padding, str):
+        raise ValueError('%s: padding_mode %r, padding %r: only zero padding given in numbers has a packed form'
+                         % (what, conv.padding_mode, conv.padding))
+
+
+class PackedConv2d(_PackedModule):
+    """y = conv2d(x, W) + bias with W[cout, cin, kh, kw] read from its packed level indices, the 2-D weight [cout, cin kh kw]
+    (qdc_conv2d_packed_f32, libqd_infer_conv.so, loaded on first use: an implicit GEMM on fp32 MFMA).  Zero padding, dilation 1,
+    groups 1; x and y are contiguous NCHW."""
+
+    def __init__(self, packed, kernel_size, stride=1, padding=0, bias=None):
+        geometry = _pair(kernel_size, 'kernel_size', 1), _pair(stride, 'stride', 1), _pair(padding, 'padding', 0)
+        super().__init__(packed, bias)
+        self.kernel_size, self.stride, self.padding = geometry
+        taps = self.kernel_size[0] * self.kernel_size[1]
+        if self.cols % taps:
+            raise ValueError('the packed weight has %d columns, no multiple of kh kw = %d' % (self.cols, taps))
+        self.in_channels, self.out_channels = self.cols // taps, self.rows
+
+    @classmethod
+    def from_conv2d(cls, conv, s, bucket_size=256, bits=None):
+        """Quantize the weight of an nn.Conv2d, seen as [cout, cin kh kw], with `s` levels per bucket: the buckets are flat, so
+        this is the packed form of what the training quantizer makes of conv.weight."""
+        _check_conv2d(conv, 'PackedConv2d.from_conv2d')
+        pk = _pack_weight(conv.weight.reshape(conv.out_channels, -1), s, bucket_size, bits, 'PackedConv2d.from_conv2d')
+        return cls(pk, tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), None if conv.bias is None else conv.bias.detach().clone())
+
+    def extra_repr(self):
+        return '%d, %d, kernel_size=%s, stride=%s, padding=%s, ' % (self.in_channels, self.out_channels, self.kernel_size, self.stride,
+                                                                   self.padding) + super().extra_repr()
+
+    def forward(self, x):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError('x must be a torch.Tensor, got %r' % type(x))
+        if x.dtype != torch.float32:
+            raise TypeError('x must be float32, got %s' % x.dtype)
+        (kh, kw), (sh, sw), (ph, pw) = self.kernel_size, self.stride, self.padding
+        if x.dim() != 4 or x.shape[1] != self.in_channels or x.shape[2] + 2 * ph < kh or x.shape[3] + 2 * pw < kw:
+            raise ValueError('x must be [N, %d, H, W] with H + %d >= %d and W + %d >= %d, got shape %s'
+                             % (self.in_channels, 2 * ph, kh, 2 * pw, kw, tuple(x.shape)))
+        _require_device(self.packed, 'PackedConv2d')
+        _require_device(x, 'PackedConv2d')
+        if x.device != self.packed.device:
+            raise ValueError('x lives on %s, the packed weight on %s' % (x.device, self.packed.device))
+        if x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError('PackedConv2d is inference only and does not differentiate through x; run under torch.no_grad(), '
+                               'or train with unpack(), the nn.Conv2d of the fake-quantized weights')
+        if _lib.on_other_device(x):
+            with torch.cuda.device(x.device):
+                return self.forward(x)
+        xc = x.detach().contiguous()                                     # channels_last is copied to NCHW
+        n, _, h, w = x.shape
+        y = torch.empty((n, self.rows, (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1), dtype=torch.float32, device=x.device)
+        from . import _infer_conv                                        # libqd_infer_conv.so: on first use only
+        _infer_conv.check(_infer_conv.load().qdc_conv2d_packed_f32(
+            self.packed.data_ptr(), self.alpha.data_ptr(), self.beta.data_ptr(), self.rows, self.in_channels, kh, kw, self.bucket_size or 0,
+            self.s, self.bits, xc.data_ptr(), n, h, w, sh, sw, ph, pw, None if self.bias is None else self.bias.data_ptr(), y.data_ptr(),
+            _lib.stream_ptr()))
+        return y
+
+    def unpack(self):
+        """An ordinary nn.Conv2d holding the fake-quantized fp32 weights (and the bias), same stride and padding."""
+        w = self._weight()
+        conv = nn.Conv2d(self.in_channels, self.rows, self.kernel_size, self.stride, self.padding, bias=self.bias is not None, device=w.device)
+        with torch.no_grad():
+            conv.weight.copy_(w.view_as(conv.weight))
+            if self.bias is not None:
+                conv.bias.copy_(self.bias)
+        return conv
+
+
+def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=None, conv=False):
+    """Replace every nn.Linear and nn.Embedding of `model` -- with conv=True every nn.Conv2d as well -- in place by its packed
+    form.  skip: names (model.named_modules()) left as they are; s: the level count, or a mapping from module name to it (every
+    replaced module must be in it); batched_from: PackedLinear's, for every Linear replaced.  A Conv2d that has no packed form
+    (groups, dilation, a padding mode) raises before anything is changed.  Returns {name: (fp32_bytes, packed_bytes)} of what
+    was replaced."""
     batched_from = _batched_from(batched_from)
     skip = set(skip)
-    todo = [(name, mod) for name, mod in model.named_modules() if isinstance(mod, (nn.Linear, nn.Embedding)) and name not in skip]
+    kinds = (nn.Linear, nn.Embedding, nn.Conv2d) if conv else (nn.Linear, nn.Embedding)
+    todo = [(name, mod) for name, mod in model.named_modules() if isinstance(mod, kinds) and name not in skip]
     unknown = skip - {name for name, _ in model.named_modules()}
     if unknown:
         raise ValueError('skip names no module of the model: %s' % sorted(unknown))
@@ -252,12 +341,18 @@ def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=Non
         if missing:
             raise ValueError('s is a mapping and has no entry for: %s' % missing)
     plan = [(name, mod, _levels_and_bits(s[name] if per_name else s, bits)) for name, mod in todo]      # every s checked before any change
+    for name, mod, _ in plan:
+        if isinstance(mod, nn.Conv2d):
+            _check_conv2d(mod, 'pack_modules: %s' % name)                 # and every convolution
     report = {}
     for name, mod, (s_i, bits_i) in plan:
         if name == '':
-            raise ValueError('the model itself is an nn.Linear / nn.Embedding: use from_linear / from_embedding')
+            raise ValueError('the model itself is an nn.Linear / nn.Embedding%s: use from_linear / from_embedding%s'
+                             % ((' / nn.Conv2d', ' / from_conv2d') if conv else ('', '')))
         if isinstance(mod, nn.Linear):
             new = PackedLinear.from_linear(mod, s_i, bucket_size, bits_i, batched_from)
+        elif isinstance(mod, nn.Conv2d):
+            new = PackedConv2d.from_conv2d(mod, s_i, bucket_size, bits_i)
         else:
             new = PackedEmbedding.from_embedding(mod, s_i, bucket_size, bits_i)
         parent_name, _, leaf = name.rpartition('.')
