@@ -1,0 +1,65 @@
+"""ctypes binding of libqd_infer_rnn.so (C ABI: include/qd_infer_rnn.h): one LSTM step from packed low-bit recurrent weights,
+both products on fp32 matrix instructions and the gate arithmetic in the same launch.
+
+A library of its own next to libqd_infer.so, libqd_infer_mm.so and libqd_infer_conv.so, with its own signature table.  Loaded
+on first use only (the first PackedLSTMCell / PackedLSTM forward); loading fails loudly when the library has not been built --
+there is no fallback implementation.
+"""
+import ctypes
+import os
+import threading
+
+from ._lib import QdLibraryMissing, c_int, c_p, i64
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, 'libqd_infer_rnn.so')
+
+ABI_VERSION = 1                # QDR_ABI_VERSION of include/qd_infer_rnn.h (tests/test_infer_rnn_abi.py compares the two)
+QDR_ERR_INVALID_ARGUMENT = -1
+
+_WEIGHT = [c_p, c_p, c_p, i64, c_int, c_int]           # packed, alpha, beta, bucket, levels, bits
+
+# symbol -> (restype, argtypes); every symbol declared in include/qd_infer_rnn.h (tests/test_infer_rnn_abi.py cross-checks)
+SIGNATURES = {
+    'qdr_abi_version': (c_int, []),
+    'qdr_target_arch': (ctypes.c_char_p, []),
+    'qdr_error_string': (ctypes.c_char_p, [c_int]),
+    'qdr_set_grid_cap': (c_int, [c_int]),                  # test hook: blocks per launch; returns the previous cap, 0 = none
+    # W_ih, W_hh, hidden, input, x, pre, h, c, batch, bias_ih, bias_hh, h_out, c_out, gates, stream
+    'qdr_lstm_cell_packed_f32': (c_int, _WEIGHT + _WEIGHT + [i64, i64, c_p, c_p, c_p, c_p, i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+}
+
+_lib = None
+_lock = threading.Lock()
+
+
+def load():
+    """Load libqd_infer_rnn.so (once).  Raises QdLibraryMissing if it has not been built."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    with _lock:
+        if _lib is not None:
+            return _lib
+        if not os.path.exists(LIB_PATH):
+            raise QdLibraryMissing(
+                'quantized_distillation_amd: %s is missing. Build it first: '
+                'python -c "import __graft_entry__ as g; g.build()" (needs hipcc, gfx950). '
+                'There is no fallback.' % LIB_PATH)
+        lib = ctypes.CDLL(LIB_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(lib, name)          # AttributeError = ABI mismatch: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+        if lib.qdr_abi_version() != ABI_VERSION:
+            raise RuntimeError('libqd_infer_rnn.so has ABI version %d, this binding is written for %d: rebuild it '
+                               '(python -c "import __graft_entry__ as g; g.build()")' % (lib.qdr_abi_version(), ABI_VERSION))
+        _lib = lib
+    return _lib
+
+
+def check(code):
+    """Raise for a non-zero return code of libqd_infer_rnn.so."""
+    if code != 0:
+        msg = load().qdr_error_string(code)
+        raise RuntimeError('qd_infer_rnn: %s (code %d)' % (msg.decode() if msg else '?', code))

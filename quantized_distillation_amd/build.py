@@ -216,10 +216,28 @@ def build_infer_conv(force=False, verbose=False):
     return _build_infer_library(srcs, _infer_conv.LIB_PATH, 'qd_infer_conv.h', INFER_MM_FLAGS, force, verbose)
 
 
+INFER_RNN_SOURCES = ['qdr_lstm.hip']                # csrc/infer/: libqd_infer_rnn.so (include/qd_infer_rnn.h), in no other source list
+
+
+def build_infer_rnn(force=False, verbose=False):
+    """libqd_infer_rnn.so next to libqd_infer_conv.so: one LSTM step from packed recurrent weights, both products on fp32 MFMA and
+    the gate arithmetic in the same launch (csrc/infer/qdr_lstm.hip, include/qd_infer_rnn.h).  INFER_MM_FLAGS, that is HIPCC_FLAGS
+    (the same weight value: correctly rounded division, no contraction -- and the header's 1 / (1 + expf(-a)) and f c + i g one
+    rounded operation at a time) with the packed-fp32 VALU forms off.  The reason INFER_MM_FLAGS gives -- one addition per
+    output -- does not hold here: the epilogue is some dozens of fp32 operations per lane.  They are kept scalar all the same:
+    the four gates of a lane are four independent chains through expf / tanhf, of which the packed forms could pair a handful
+    of multiplies and adds at the most, and the header words every operation as one scalar fp32 operation.  The build with the
+    forms on was not made."""
+    from . import _infer, _infer_rnn
+    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_RNN_SOURCES]
+    return _build_infer_library(srcs, _infer_rnn.LIB_PATH, 'qd_infer_rnn.h', INFER_MM_FLAGS, force, verbose)
+
+
 if __name__ == '__main__':
     print(build_extension(force=True, verbose=True))
     print(build_infer(force=True, verbose=True))
     print(build_infer_mm(force=True, verbose=True))
     print(build_infer_conv(force=True, verbose=True))
+    print(build_infer_rnn(force=True, verbose=True))
     print(build_glue(force=True, verbose=True))
     print(build_host(force=True, verbose=True))

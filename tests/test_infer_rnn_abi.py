@@ -1,0 +1,127 @@
+"""libqd_infer_rnn.so (include/qd_infer_rnn.h: an LSTM step from packed weights, both products on fp32 MFMA, gates in the same launch)
+builds for gfx950 without a GPU, exports exactly the header's symbols, keeps its kernel free of scratch and spills and refuses
+bad arguments before it touches a device; PackedLSTMCell, PackedLSTM and pack_modules(rnn=True) validate before any launch."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+from torch import nn
+
+from quantized_distillation_amd import _infer_rnn, codec, packed_layers
+from quantized_distillation_amd import build as qb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'qd_infer_rnn.h')
+
+
+@pytest.fixture(scope='module')
+def lib():
+    qb.build_infer_rnn()
+    return _infer_rnn.load()
+
+
+def test_header_binding_and_exports_agree(lib):
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    syms = sorted(set(re.findall(r'\b(qdr_[a-z0-9_]+)\s*\(', text)))
+    assert syms == sorted(_infer_rnn.SIGNATURES) and len(syms) == 5
+    out = subprocess.check_output(['nm', '-D', '--defined-only', _infer_rnn.LIB_PATH], text=True)
+    assert sorted(set(re.findall(r' T (qd[a-z]?_[a-z0-9_]+)', out))) == syms                  # and nothing named qd_, qdi_, qdm_ or qdc_
+    assert int(re.search(r'#define QDR_ABI_VERSION (\d+)', open(HEADER).read()).group(1)) == _infer_rnn.ABI_VERSION == lib.qdr_abi_version() == 1
+    assert lib.qdr_target_arch() == b'gfx950'
+    assert lib.qdr_error_string(0) == b'success' and b'invalid' in lib.qdr_error_string(-1)
+    assert not set(qb.INFER_RNN_SOURCES) & (set(qb.SOURCES) | set(qb.INFER_SOURCES) | set(qb.INFER_MM_SOURCES) | set(qb.INFER_CONV_SOURCES))
+    blob = open(_infer_rnn.LIB_PATH, 'rb').read()
+    assert set(re.findall(rb'hipv4-amdgcn-amd-amdhsa--(gfx[0-9a-z]+)', blob)) == {b'gfx950'}
+
+
+def test_the_kernel_uses_no_scratch_and_spills_nothing(lib):
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import kernel_meta
+    ks = kernel_meta.kernels(_infer_rnn.LIB_PATH)
+    assert len(ks) == 1 and 'k_lstm_cell_mm' in ks[0]['name']
+    k = ks[0]
+    assert (k.get('private_segment_fixed_size', 0), k.get('vgpr_spill_count', 0), k.get('sgpr_spill_count', 0)) == (0, 0, 0), k
+    assert k.get('uses_dynamic_stack') != 'true' and k['group_segment_fixed_size'] <= 64 * 1024, k
+
+
+def test_refusals_and_empty_calls_without_a_device(lib):
+    """Every refusal of the header, with pointers that are never dereferenced: -1 without a launch."""
+    assert lib.qdr_set_grid_cap(3) == 0 and lib.qdr_set_grid_cap(0) == 3 and lib.qdr_set_grid_cap(-5) == 0
+    P = 4096                                                               # a well-aligned non-NULL address, never read
+    ih = dict(packed_ih=P, alpha_ih=P, beta_ih=P, bucket_ih=4, levels_ih=16, bits_ih=4)
+    hh = dict(packed_hh=P, alpha_hh=P, beta_hh=P, bucket_hh=4, levels_hh=16, bits_hh=4)
+    rest = dict(hidden=5, input=7, x=P, pre=None, h=P, c=P, batch=3, bias_ih=P, bias_hh=P, h_out=2 * P, c_out=P, gates=P)
+    order = list(ih) + list(hh) + list(rest)
+
+    def cell(**kw):
+        args = dict(ih, **hh, **rest)
+        args.update(kw)
+        return lib.qdr_lstm_cell_packed_f32(*[args[k] for k in order], None)
+
+    pre_mode = dict(x=None, pre=P, bias_ih=None)
+    bad = [dict(hidden=-1), dict(input=-1), dict(batch=-1), dict(hidden=2 ** 61), dict(hidden=2 ** 30, batch=2 ** 40), dict(input=2 ** 40, batch=2 ** 40),
+           dict(hidden=2 ** 40, input=2 ** 40),                                                    # the element count of W_ih
+           dict(x=P, pre=P, bias_ih=None), dict(x=None, pre=None), dict(x=None, pre=P), dict(h_out=P),   # both, neither, bias_ih in pre mode, h_out == h
+           dict(packed_ih=None), dict(alpha_ih=None), dict(beta_ih=None), dict(pre_mode, packed_hh=None), dict(alpha_hh=None), dict(beta_hh=None)]
+    for sfx in ('_ih', '_hh'):                                             # everything describe refuses, of either weight
+        bad += [{'levels' + sfx: 1}, {'levels' + sfx: 257, 'bits' + sfx: 8}, {'bits' + sfx: 0}, {'bits' + sfx: 9, 'levels' + sfx: 2},
+                {'levels' + sfx: 17}, {'levels' + sfx: 3, 'bits' + sfx: 1}, {'bucket' + sfx: -1},
+                {'packed' + sfx: P + 2}, {'alpha' + sfx: P + 1}, {'beta' + sfx: P + 2}]
+    bad += [{k: None} for k in ('h', 'c', 'h_out', 'c_out')] + [{k: P + 2} for k in ('x', 'h', 'c', 'bias_ih', 'bias_hh', 'h_out', 'c_out', 'gates')]
+    bad += [dict(pre_mode, pre=P + 1), dict(pre_mode, levels_hh=1), dict(pre_mode, h=None)]
+    for kw in bad:
+        assert cell(**kw) == -1, kw
+    assert cell(batch=0, x=None, h=None, c=None, h_out=None, c_out=None, gates=None) == 0
+    assert cell(hidden=0, packed_hh=None, alpha_hh=None, beta_hh=None, h_out=None, c_out=None, gates=None) == 0
+    # pre mode does not look at the W_ih arguments or at `input`
+    assert cell(**dict(pre_mode, batch=0, packed_ih=None, alpha_ih=P + 1, levels_ih=0, bits_ih=77, input=-3)) == 0
+
+
+def _packed(rows, cols):
+    n = rows * cols
+    return codec.PackedUniform(torch.zeros(n // 2, dtype=torch.uint8), torch.ones(n // 16), torch.zeros(n // 16), (rows, cols), 16, 16, 4)
+
+
+def test_the_modules_are_validated_before_any_launch():
+    PC, PL = packed_layers.PackedLSTMCell, packed_layers.PackedLSTM
+    cell = PC(_packed(16, 8), _packed(16, 4), torch.zeros(16), torch.zeros(16))
+    assert (cell.input_size, cell.hidden_size) == (8, 4) and cell.fp32_nbytes == 4 * (128 + 64 + 32)
+    assert cell.nbytes == (64 + 8 * 8 + 64) + (32 + 4 * 8 + 64)
+    for args in ((_packed(16, 8), _packed(16, 8)), (_packed(32, 8), _packed(16, 4)), (_packed(16, 8), _packed(16, 4), torch.zeros(4))):
+        with pytest.raises(ValueError):
+            PC(*args)
+    z = torch.zeros
+    for x, state, err in ((z(3, 7), None, ValueError), (z(3, 8, 1), None, ValueError), (z(3, 8), (z(3, 5), z(3, 4)), ValueError), (z(3, 8), z(3, 4), TypeError),
+                          (z(3, 8, dtype=torch.float64), None, TypeError), ([1.0], None, TypeError), (z(3, 8), (z(3, 4), z(3, 4)), NotImplementedError)):
+        with pytest.raises(err):
+            cell(x, state)                                                 # the last one: CPU tensors, there is no CPU path
+    lstm = PL([cell, PC(_packed(16, 8), _packed(16, 4)), PC(_packed(16, 8), _packed(16, 4)), PC(_packed(16, 8), _packed(16, 4))], bidirectional=True)
+    assert (lstm.num_layers, lstm.input_size, lstm.hidden_size) == (2, 8, 4) and lstm.nbytes == cell.nbytes + 3 * (cell.nbytes - 128)
+    for cells, kw in (([], {}), ([cell], dict(bidirectional=True)), ([cell, cell], {}), ([nn.LSTMCell(8, 4)], {})):
+        with pytest.raises(ValueError):
+            PL(cells, **kw)                                                # [cell, cell]: layer 1 takes hidden = 4 inputs, not 8
+    packed_seq = nn.utils.rnn.pack_padded_sequence(z(5, 2, 8), [5, 3])
+    for x, hx, err in ((packed_seq, None, TypeError), (z(5, 2, 7), None, ValueError), (z(0, 2, 8), None, ValueError), (z(5, 2, 8), (z(4, 2, 4), z(2, 2, 4)), ValueError),
+                       (z(5, 2, 8), z(4, 2, 4), TypeError), (z(5, 2, 8), None, NotImplementedError)):
+        with pytest.raises(err):
+            lstm(x, hx)
+    with pytest.raises(ValueError, match='proj_size'):
+        PL.from_lstm(nn.LSTM(8, 4, proj_size=2), 16)                       # before the device check and before packing
+    with pytest.raises(TypeError):
+        PC.from_lstm_cell(nn.GRUCell(8, 4), 16)
+
+
+def test_pack_modules_and_rnn():
+    model = nn.ModuleDict(dict(enc=nn.LSTM(8, 4), cell=nn.LSTMCell(8, 4)))
+    before = dict(model.named_modules())
+    assert packed_layers.pack_modules(model, 16) == {} and dict(model.named_modules()) == before   # without rnn=True left alone
+    with pytest.raises(NotImplementedError):
+        packed_layers.pack_modules(model, 16, rnn=True)                    # with it they are taken: CPU weights have no packed form
+    model = nn.ModuleDict(dict(lin=nn.Linear(8, 4), cell=nn.LSTMCell(8, 4), enc=nn.LSTM(8, 4, proj_size=2)))
+    before = dict(model.named_modules())
+    with pytest.raises(ValueError, match='proj_size'):
+        packed_layers.pack_modules(model, 16, rnn=True)
+    assert dict(model.named_modules()) == before                           # nothing was replaced, the Linear in front included
