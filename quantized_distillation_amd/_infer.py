@@ -5,9 +5,8 @@ and stays that.  Loading fails loudly when the library has not been built -- the
 """
 import ctypes
 import os
-import threading
 
-from ._lib import QdLibraryMissing, c_int, c_p, i64
+from ._lib import binding, c_int, c_p, i64
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libqd_infer.so')
@@ -26,37 +25,5 @@ SIGNATURES = {
     'qdi_linear_packed_f32': (c_int, [c_p, c_p, c_p, i64, i64, i64, c_int, c_int, c_p, i64, c_p, c_p, c_p]),
 }
 
-_lib = None
-_lock = threading.Lock()
-
-
-def load():
-    """Load libqd_infer.so (once).  Raises QdLibraryMissing if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        if not os.path.exists(LIB_PATH):
-            raise QdLibraryMissing(
-                'quantized_distillation_amd: %s is missing. Build it first: '
-                'python -c "import __graft_entry__ as g; g.build()" (needs hipcc, gfx950). '
-                'There is no fallback: decode with PackedUniform.unpack() to run without it.' % LIB_PATH)
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)          # AttributeError = ABI mismatch: fail loudly
-            fn.restype = res
-            fn.argtypes = args
-        if lib.qdi_abi_version() != ABI_VERSION:
-            raise RuntimeError('libqd_infer.so has ABI version %d, this binding is written for %d: rebuild it '
-                               '(python -c "import __graft_entry__ as g; g.build()")' % (lib.qdi_abi_version(), ABI_VERSION))
-        _lib = lib
-    return _lib
-
-
-def check(code):
-    """Raise for a non-zero return code of libqd_infer.so."""
-    if code != 0:
-        msg = load().qdi_error_string(code)
-        raise RuntimeError('qd_infer: %s (code %d)' % (msg.decode() if msg else '?', code))
+_lib = None                    # the loaded library, set by load()
+load, check = binding(__name__, 'qdi', 'There is no fallback: decode with PackedUniform.unpack() to run without it.')

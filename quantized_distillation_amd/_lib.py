@@ -198,6 +198,49 @@ def load():
     return _lib
 
 
+def binding(module_name, prefix, missing_hint):
+    """(load, check) of one inference library for its binding module (_infer, _infer_mm, _infer_conv, _infer_rnn).  The module
+    holds the tables -- LIB_PATH, ABI_VERSION, SIGNATURES -- and the loaded library (`_lib`, None until first use); they are
+    read from it at every call, so a test may point LIB_PATH elsewhere.  prefix: of the library's symbols ('qdi');
+    missing_hint: the last sentence of the QdLibraryMissing message."""
+    import sys
+    lock = threading.Lock()
+    mod = sys.modules[module_name]
+    name = os.path.basename(mod.LIB_PATH)
+
+    def load():
+        """Load the library (once).  Raises QdLibraryMissing if it has not been built."""
+        if mod._lib is not None:
+            return mod._lib
+        with lock:
+            if mod._lib is not None:
+                return mod._lib
+            if not os.path.exists(mod.LIB_PATH):
+                raise QdLibraryMissing(
+                    'quantized_distillation_amd: %s is missing. Build it first: '
+                    'python -c "import __graft_entry__ as g; g.build()" (needs hipcc, gfx950). '
+                    '%s' % (mod.LIB_PATH, missing_hint))
+            lib = ctypes.CDLL(mod.LIB_PATH)
+            for sym, (res, args) in mod.SIGNATURES.items():
+                fn = getattr(lib, sym)           # AttributeError = ABI mismatch: fail loudly
+                fn.restype = res
+                fn.argtypes = args
+            version = getattr(lib, prefix + '_abi_version')()
+            if version != mod.ABI_VERSION:
+                raise RuntimeError('%s has ABI version %d, this binding is written for %d: rebuild it '
+                                   '(python -c "import __graft_entry__ as g; g.build()")' % (name, version, mod.ABI_VERSION))
+            mod._lib = lib
+        return mod._lib
+
+    def check(code):
+        """Raise for a non-zero return code of the library."""
+        if code != 0:
+            msg = getattr(load(), prefix + '_error_string')(code)
+            raise RuntimeError('%s: %s (code %d)' % (name[len('lib'):-len('.so')], msg.decode() if msg else '?', code))
+
+    return load, check
+
+
 # the entry points libqd_host.so implements (the per-call functions and the Huffman checkpoint codec; multi-tensor, packed
 # codec, order statistics and the 'absmax' / 'absnorm' scalings exist for device tensors only)
 HOST_SYMBOLS = ('qd_abi_version', 'qd_target_arch', 'qd_error_string', 'qd_workspace_bytes', 'qd_num_buckets', 'qd_padded_length',

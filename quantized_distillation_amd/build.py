@@ -160,22 +160,41 @@ def build_host(force=False, verbose=False):
     return out
 
 
-INFER_SOURCES = ['qdi_layers.hip']                  # csrc/infer/: libqd_infer.so (include/qd_infer.h), nothing of it in SOURCES
+# HIPCC_FLAGS, and the packed-fp32 VALU forms (v_pk_add / mul / fma_f32) switched off for the device code of the MFMA libraries.
+# libqd_infer_mm.so: its arithmetic is MFMA plus ONE fp32 addition per output (the bias), which is to stay one scalar v_add_f32
+# per element, as the header words it.  Nothing is lost: there is no other fp32 VALU arithmetic on the hot path.
+INFER_MM_FLAGS = HIPCC_FLAGS + ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
+
+# The inference libraries, each next to libqd_hip.so and one hipcc call from sources under csrc/infer/ that are in no other
+# row and not in SOURCES: (library, sources, public header under include/, flags, binding module).  Every row has HIPCC_FLAGS:
+# the weight value needs the same correctly rounded division and no contraction as build_extension.
+INFER_LIBRARIES = [
+    # Linear and Embedding from packed weights, row-wise sweeps without MFMA
+    ('libqd_infer.so', ['qdi_layers.hip'], 'qd_infer.h', HIPCC_FLAGS, '_infer'),
+    # the batched Linear layer on fp32 MFMA
+    ('libqd_infer_mm.so', ['qdm_linear.hip'], 'qd_infer_mm.h', INFER_MM_FLAGS, '_infer_mm'),
+    # nn.Conv2d as an implicit GEMM on fp32 MFMA.  INFER_MM_FLAGS: the one fp32 VALU addition per output is the bias here too.
+    ('libqd_infer_conv.so', ['qdc_conv2d.hip'], 'qd_infer_conv.h', INFER_MM_FLAGS, '_infer_conv'),
+    # One LSTM step, both products on fp32 MFMA and the gate arithmetic in the same launch.  INFER_MM_FLAGS, that is HIPCC_FLAGS
+    # (the header's 1 / (1 + expf(-a)) and f c + i g one rounded operation at a time) with the packed-fp32 VALU forms off.  The
+    # reason INFER_MM_FLAGS gives -- one addition per output -- does not hold here: the epilogue is some dozens of fp32 operations
+    # per lane.  They are kept scalar all the same: the four gates of a lane are four independent chains through expf / tanhf,
+    # of which the packed forms could pair a handful of multiplies and adds at the most, and the header words every operation
+    # as one scalar fp32 operation.  The build with the forms on was not made.
+    ('libqd_infer_rnn.so', ['qdr_lstm.hip'], 'qd_infer_rnn.h', INFER_MM_FLAGS, '_infer_rnn'),
+]
+INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES = (row[1] for row in INFER_LIBRARIES)
 
 
-def build_infer(force=False, verbose=False):
-    """libqd_infer.so next to libqd_hip.so: Linear and Embedding from packed weights (csrc/infer/, include/qd_infer.h).  The
-    flags of build_extension (the weight value needs the same correctly rounded division and no contraction), the same
-    stale check against every header, and an atomic replace of a complete file."""
+def build_infer_library(library, force=False, verbose=False):
+    """One row of INFER_LIBRARIES: stale against its sources, every header under csrc/ and csrc/infer/, its public header and
+    this file; an atomic replace of a complete file at the path its binding module loads."""
+    import importlib
+
     from . import _infer
-    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_SOURCES]
-    return _build_infer_library(srcs, _infer.LIB_PATH, 'qd_infer.h', HIPCC_FLAGS, force, verbose)
-
-
-def _build_infer_library(srcs, out, header, flags, force, verbose):
-    """One hipcc call from sources under csrc/infer/ to a library; stale against the sources, every header under csrc/ and
-    csrc/infer/, the public header and this file."""
-    from . import _infer
+    _name, sources, header, flags, module = next(row for row in INFER_LIBRARIES if row[0] == library)
+    out = importlib.import_module('.' + module, __package__).LIB_PATH
+    srcs = [os.path.join(_infer.CSRC, f) for f in sources]
     deps = (srcs + _headers() + [os.path.join(_infer.CSRC, f) for f in sorted(os.listdir(_infer.CSRC)) if f.endswith('.h')]
             + [os.path.join(_lib.INCLUDE, header)])
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
@@ -189,55 +208,25 @@ def _build_infer_library(srcs, out, header, flags, force, verbose):
     return out
 
 
-INFER_MM_SOURCES = ['qdm_linear.hip']               # csrc/infer/: libqd_infer_mm.so (include/qd_infer_mm.h), nothing of it in SOURCES or INFER_SOURCES
-# HIPCC_FLAGS, and the packed-fp32 VALU forms (v_pk_add / mul / fma_f32) switched off for the device code of this library: its
-# arithmetic is MFMA plus ONE fp32 addition per output (the bias), which is to stay one scalar v_add_f32 per element, as the
-# header words it.  Nothing is lost: there is no other fp32 VALU arithmetic on the hot path.
-INFER_MM_FLAGS = HIPCC_FLAGS + ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
+def build_infer(force=False, verbose=False):
+    return build_infer_library('libqd_infer.so', force, verbose)
 
 
 def build_infer_mm(force=False, verbose=False):
-    """libqd_infer_mm.so next to libqd_infer.so: the batched Linear layer from packed weights on fp32 MFMA (csrc/infer/
-    qdm_linear.hip, include/qd_infer_mm.h).  HIPCC_FLAGS (the same weight value: correctly rounded division, no contraction),
-    the stale check and the atomic replace of build_infer."""
-    from . import _infer, _infer_mm
-    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_MM_SOURCES]
-    return _build_infer_library(srcs, _infer_mm.LIB_PATH, 'qd_infer_mm.h', INFER_MM_FLAGS, force, verbose)
-
-
-INFER_CONV_SOURCES = ['qdc_conv2d.hip']             # csrc/infer/: libqd_infer_conv.so (include/qd_infer_conv.h), in no other source list
+    return build_infer_library('libqd_infer_mm.so', force, verbose)
 
 
 def build_infer_conv(force=False, verbose=False):
-    """libqd_infer_conv.so next to libqd_infer_mm.so: nn.Conv2d from packed weights as an implicit GEMM on fp32 MFMA (csrc/infer/
-    qdc_conv2d.hip, include/qd_infer_conv.h).  INFER_MM_FLAGS: the one fp32 VALU addition per output is the bias here too."""
-    from . import _infer, _infer_conv
-    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_CONV_SOURCES]
-    return _build_infer_library(srcs, _infer_conv.LIB_PATH, 'qd_infer_conv.h', INFER_MM_FLAGS, force, verbose)
-
-
-INFER_RNN_SOURCES = ['qdr_lstm.hip']                # csrc/infer/: libqd_infer_rnn.so (include/qd_infer_rnn.h), in no other source list
+    return build_infer_library('libqd_infer_conv.so', force, verbose)
 
 
 def build_infer_rnn(force=False, verbose=False):
-    """libqd_infer_rnn.so next to libqd_infer_conv.so: one LSTM step from packed recurrent weights, both products on fp32 MFMA and
-    the gate arithmetic in the same launch (csrc/infer/qdr_lstm.hip, include/qd_infer_rnn.h).  INFER_MM_FLAGS, that is HIPCC_FLAGS
-    (the same weight value: correctly rounded division, no contraction -- and the header's 1 / (1 + expf(-a)) and f c + i g one
-    rounded operation at a time) with the packed-fp32 VALU forms off.  The reason INFER_MM_FLAGS gives -- one addition per
-    output -- does not hold here: the epilogue is some dozens of fp32 operations per lane.  They are kept scalar all the same:
-    the four gates of a lane are four independent chains through expf / tanhf, of which the packed forms could pair a handful
-    of multiplies and adds at the most, and the header words every operation as one scalar fp32 operation.  The build with the
-    forms on was not made."""
-    from . import _infer, _infer_rnn
-    srcs = [os.path.join(_infer.CSRC, f) for f in INFER_RNN_SOURCES]
-    return _build_infer_library(srcs, _infer_rnn.LIB_PATH, 'qd_infer_rnn.h', INFER_MM_FLAGS, force, verbose)
+    return build_infer_library('libqd_infer_rnn.so', force, verbose)
 
 
 if __name__ == '__main__':
     print(build_extension(force=True, verbose=True))
-    print(build_infer(force=True, verbose=True))
-    print(build_infer_mm(force=True, verbose=True))
-    print(build_infer_conv(force=True, verbose=True))
-    print(build_infer_rnn(force=True, verbose=True))
+    for row in INFER_LIBRARIES:
+        print(build_infer_library(row[0], force=True, verbose=True))
     print(build_glue(force=True, verbose=True))
     print(build_host(force=True, verbose=True))

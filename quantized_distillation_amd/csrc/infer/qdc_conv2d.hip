@@ -14,7 +14,7 @@
 //   operands  swapped against k_linear_mm: A = W (a lane gives w[r0 + l % 16][k]), B = the gathered input (column l % 16 is a
 //             pixel), so D[i][j] has j = l % 16 along PIXELS, the contiguous axis of an NCHW output: the 16 lanes of a row
 //             group store 64 contiguous bytes of y[n][co] wherever their 16 pixels lie in one image.
-//   weights   ws[16][68], the staging of k_linear_mm: thread t decodes the group of four [4 (t % 16), + 4) of row t / 16, one
+//   weights   ws[16][68], the staging of qdi_mm.h (weight_bucket, weight_step): thread t decodes the group of four [4 (t % 16), + 4) of row t / 16, one
 //             bucket search per thread and tile, steps of 64 elements from there; fetch4 (loads only) before the MFMAs of the
 //             slab before, finish4 after them.
 //   gather    xs[64][260], K-MAJOR: row = column of the slab, 256 pixels + 4 floats of padding.  Each wave stages ITS OWN 64
@@ -35,7 +35,7 @@
 //   offsets   of x and y are unsigned and wrap (a window that starts left of or above the image has a "negative" first
 //             offset; the offsets that are LOADED are the true ones): 32 bits wide where x and y hold fewer than 2^31 elements
 //             each, 64 bits otherwise -- one kernel, the width a by-value argument.
-#include "qdi_packed.h"       // Packed, describe, divmod, build_quotients, fetch4 / finish4: shared with the other two libraries
+#include "qdi_mm.h"           // the weight pieces of the K walk; through it qdi_packed.h: Packed, describe, the decode, the host helpers
 
 #include "../../../include/qd_infer_conv.h"
 
@@ -43,19 +43,8 @@ using namespace qd;
 
 namespace {
 
-constexpr int kSlab = 64;              // columns of a slab
-constexpr int kRows = 16;              // output channels of a tile: one MFMA block
 constexpr int kPix = 256;              // output pixels of a tile: 64 per wave
-constexpr int kStride = 68;            // floats per row of ws (k_linear_mm's)
 constexpr int kXS = 260;               // floats per row of xs: 256 pixels + 4, so that k-rows 4 apart lie 16 banks apart
-
-int g_grid_cap = 0;                    // qdc_set_grid_cap: 0 = none
-
-int capped(int64_t blocks, int64_t own_cap) {
-    if (blocks > own_cap) blocks = own_cap;
-    if (g_grid_cap >= 1 && blocks > g_grid_cap) blocks = g_grid_cap;
-    return blocks < 1 ? 1 : (int)blocks;
-}
 
 // By-value geometry of a call.
 struct Conv {
@@ -96,8 +85,8 @@ __device__ __forceinline__ void conv_tiles(const Packed& P, const Conv& C, const
         // under the same test in fetch and in commit.  Likewise a lane without a pixel (!valid) or a window position outside the
         // image carries an offset that is never turned into an address that is read.
         int64_t e = (r0 + wr) * K + wc;
-        int64_t bkt = 0, rem = 0;
-        if (wrow && wc < K) divmod(e, P.bucket, P.small, bkt, rem);
+        int64_t bkt, rem;
+        weight_bucket(P, e, wrow && wc < K, bkt, rem);
         const U pix = m0 + 64 * wave + lane;
         const bool valid = pix < M;
         U img = 0, r = 0, xb = 0;                                        // image, pixel inside it, offset of the window's first element in x
@@ -145,6 +134,8 @@ __device__ __forceinline__ void conv_tiles(const Packed& P, const Conv& C, const
         };
         // The same slab from the registers into LDS, zeros wherever nothing was loaded; then (ca, cb, coff) are 64 columns on.
         auto commit = [&](int kl) {
+            // weight_commit of qdi_mm.h, left written out: called from here the compiler schedules this kernel's prologue differently
+            // (profiles/infer_mm_dedup_device_code.txt), and the device code is to stay what it was.
             const int nw = kl - wc;                                      // columns from this group's first to the end of the row
             float wv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if (wrow && nw > 0) finish4(P, qtab, lo, hi, a0, b0, e, bkt, rem, nw < 4 ? nw : 4, wv);
@@ -185,9 +176,7 @@ __device__ __forceinline__ void conv_tiles(const Packed& P, const Conv& C, const
             if (kl <= 0) break;
             commit(kl);
             __syncthreads();
-            bkt += C.step_q; rem += C.step_r;                            // 64 columns on: the bucket of the next slab's group
-            if (rem >= P.bucket) { rem -= P.bucket; ++bkt; }
-            e += kSlab;
+            weight_step(P, C.step_q, C.step_r, e, bkt, rem);
             klp = kl;
             kleft -= kSlab;
         }
@@ -235,18 +224,8 @@ extern "C" {
 int qdc_abi_version(void) { return QDC_ABI_VERSION; }
 const char* qdc_target_arch(void) { return "gfx950"; }
 
-const char* qdc_error_string(int code) {
-    if (code == 0) return "success";
-    if (code == QDC_ERR_INVALID_ARGUMENT) return "invalid argument";
-    if (code > 0) return hipGetErrorString((hipError_t)code);
-    return "unknown error";
-}
-
-int qdc_set_grid_cap(int blocks) {
-    const int prev = g_grid_cap;
-    g_grid_cap = blocks >= 1 ? blocks : 0;
-    return prev;
-}
+const char* qdc_error_string(int code) { return error_string(code, QDC_ERR_INVALID_ARGUMENT); }
+int qdc_set_grid_cap(int blocks) { return set_grid_cap(blocks); }
 
 int qdc_conv2d_packed_f32(const uint8_t* packed, const float* alpha, const float* beta, int64_t cout, int64_t cin, int kh, int kw,
                           int64_t bucket, int levels, int bits, const float* x, int64_t batch, int64_t h, int64_t w, int stride_h,
@@ -258,7 +237,7 @@ int qdc_conv2d_packed_f32(const uint8_t* packed, const float* alpha, const float
     if (__builtin_mul_overflow(cin, (int64_t)kh * kw, &K)) return QDC_ERR_INVALID_ARGUMENT;
     Packed P;
     if (!describe(P, packed, alpha, beta, cout, K, bucket, levels, bits)) return QDC_ERR_INVALID_ARGUMENT;
-    if ((((uintptr_t)x) & 3) || (((uintptr_t)bias) & 3) || (((uintptr_t)y) & 3)) return QDC_ERR_INVALID_ARGUMENT;
+    if (misaligned(x) || misaligned(bias) || misaligned(y)) return QDC_ERR_INVALID_ARGUMENT;
     if (__builtin_add_overflow(h, 2 * (int64_t)pad_h, &hp) || __builtin_add_overflow(w, 2 * (int64_t)pad_w, &wp) || hp < kh || wp < kw)
         return QDC_ERR_INVALID_ARGUMENT;
     const int64_t oh = (hp - kh) / stride_h + 1, ow = (wp - kw) / stride_w + 1;

@@ -11,21 +11,13 @@
 // division the codec uses (qd_codec.hip: k_unpack_any), so a weight is bit for bit what qd_unpack_uniform_f32 writes and
 // no lane divides per element.  The bucket of an element is found with one division per lane and row (linear) or per
 // group of four (embedding); inside a group an element that leaves the group's first bucket steps on (three buckets at the most).
-#include "qdi_packed.h"       // Packed, describe, stream_bits, divmod, build_quotients, decode4: shared with qdm_linear.hip
+#include "qdi_packed.h"       // Packed, describe, stream_bits, divmod, build_quotients, decode4, the host helpers: shared with the MFMA libraries
 
 #include "../../../include/qd_infer.h"
 
 using namespace qd;
 
 namespace {
-
-int g_grid_cap = 0;                                                    // qdi_set_grid_cap: 0 = none
-
-int capped(int64_t blocks, int64_t own_cap) {
-    if (blocks > own_cap) blocks = own_cap;
-    if (g_grid_cap >= 1 && blocks > g_grid_cap) blocks = g_grid_cap;
-    return blocks < 1 ? 1 : (int)blocks;
-}
 
 __global__ __launch_bounds__(256) void k_embedding(Packed P, const int64_t* idx, int64_t count, float* out) {
     __shared__ float qtab[256];
@@ -125,24 +117,14 @@ extern "C" {
 int qdi_abi_version(void) { return QDI_ABI_VERSION; }
 const char* qdi_target_arch(void) { return "gfx950"; }
 
-const char* qdi_error_string(int code) {
-    if (code == 0) return "success";
-    if (code == QDI_ERR_INVALID_ARGUMENT) return "invalid argument";
-    if (code > 0) return hipGetErrorString((hipError_t)code);
-    return "unknown error";
-}
-
-int qdi_set_grid_cap(int blocks) {
-    const int prev = g_grid_cap;
-    g_grid_cap = blocks >= 1 ? blocks : 0;
-    return prev;
-}
+const char* qdi_error_string(int code) { return error_string(code, QDI_ERR_INVALID_ARGUMENT); }
+int qdi_set_grid_cap(int blocks) { return set_grid_cap(blocks); }
 
 int qdi_embedding_packed_f32(const uint8_t* packed, const float* alpha, const float* beta, int64_t rows, int64_t cols, int64_t bucket,
                              int levels, int bits, const int64_t* idx, int64_t count, float* out, void* stream) {
     Packed P;
     if (!describe(P, packed, alpha, beta, rows, cols, bucket, levels, bits) || count < 0) return QDI_ERR_INVALID_ARGUMENT;
-    if ((((uintptr_t)idx) & 7) || (((uintptr_t)out) & 3)) return QDI_ERR_INVALID_ARGUMENT;
+    if ((((uintptr_t)idx) & 7) || misaligned(out)) return QDI_ERR_INVALID_ARGUMENT;
     int64_t nout = 0;
     if (__builtin_mul_overflow(count, (cols + 3) >> 2, &nout) || nout > INT64_MAX / 4) return QDI_ERR_INVALID_ARGUMENT;
     if (count == 0 || cols == 0) return 0;
@@ -156,7 +138,7 @@ int qdi_linear_packed_f32(const uint8_t* packed, const float* alpha, const float
                           int levels, int bits, const float* x, int64_t m, const float* bias, float* y, void* stream) {
     Packed P;
     if (!describe(P, packed, alpha, beta, rows, cols, bucket, levels, bits) || m < 0) return QDI_ERR_INVALID_ARGUMENT;
-    if ((((uintptr_t)x) & 3) || (((uintptr_t)bias) & 3) || (((uintptr_t)y) & 3)) return QDI_ERR_INVALID_ARGUMENT;
+    if (misaligned(x) || misaligned(bias) || misaligned(y)) return QDI_ERR_INVALID_ARGUMENT;
     int64_t t = 0;
     if (__builtin_mul_overflow(m, rows, &t) || __builtin_mul_overflow(m, cols, &t)) return QDI_ERR_INVALID_ARGUMENT;
     if (m == 0 || rows == 0) return 0;

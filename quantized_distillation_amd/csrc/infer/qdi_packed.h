@@ -1,7 +1,9 @@
 // qdi_packed.h -- the packed weight of include/qd_infer.h as the inference kernels see it: its by-value description, the
-// argument checks every entry point starts with, and the decode of a group of four consecutive weights.  Shared by
-// qdi_layers.hip (libqd_infer.so) and qdm_linear.hip (libqd_infer_mm.so): one header for the weight value (decode4, and its
-// loop again in finish4 -- see there), so both libraries give, bit for bit, what qd_unpack_uniform_f32 writes.
+// argument checks every entry point starts with, the decode of a group of four consecutive weights, and the few host lines
+// every entry file needs (grid cap, error string, alignment test).  Shared by all four inference libraries -- qdi_layers.hip
+// (libqd_infer.so) directly; qdm_linear.hip (libqd_infer_mm.so), qdc_conv2d.hip (libqd_infer_conv.so) and qdr_lstm.hip
+// (libqd_infer_rnn.so) through qdi_mm.h: one header for the weight value (decode4, and its loop again in finish4 -- see there),
+// so every library gives, bit for bit, what qd_unpack_uniform_f32 writes.
 //
 // Everything sits in an unnamed namespace on purpose: each library is one translation unit, nothing here is exported, and
 // the kernels' mangled names (which carry Packed) stay what they were when these lines lived in qdi_layers.hip.
@@ -74,7 +76,7 @@ __device__ __forceinline__ void decode4(const Packed& P, const float* qtab, int6
     }
 }
 
-// decode4 in two halves, for a kernel that issues a group's loads a slab ahead of its arithmetic (qdm_linear.hip).
+// decode4 in two halves, for the kernels that issue a group's loads a slab ahead of its arithmetic (qdi_mm.h).
 // fetch4 is LOADS ONLY: the two aligned stream words of stream_bits' common case, unshifted, and the (alpha, beta) of the
 // first element's bucket.  Nothing is computed from a loaded value, so the compiler has no reason to wait for one before the
 // caller's next instruction (with the shift in here every group's loads were followed by s_waitcnt vmcnt(0): one full memory
@@ -121,13 +123,16 @@ __device__ __forceinline__ void finish4(const Packed& P, const float* qtab, uint
     }
 }
 
+// A pointer to fp32 data (or the packed stream, read as 32-bit words) that is not 4-byte aligned; NULL is aligned.
+inline bool misaligned(const void* p) { return (((uintptr_t)p) & 3) != 0; }
+
 // The checks of include/qd_infer.h that concern the weight alone, and its description.  false: refuse the call.
 inline bool describe(Packed& P, const uint8_t* packed, const float* alpha, const float* beta, int64_t rows, int64_t cols, int64_t bucket,
                      int levels, int bits) {
     if (rows < 0 || cols < 0 || bucket < 0 || levels < 2 || levels > 256 || bits < 1 || bits > 8 || levels > (1 << bits)) return false;
     int64_t n = 0, nbits = 0;
     if (__builtin_mul_overflow(rows, cols, &n) || __builtin_mul_overflow(n, (int64_t)bits, &nbits) || nbits > INT64_MAX - 64) return false;
-    if ((((uintptr_t)packed) & 3) || (((uintptr_t)alpha) & 3) || (((uintptr_t)beta) & 3)) return false;
+    if (misaligned(packed) || misaligned(alpha) || misaligned(beta)) return false;
     P.packed = packed; P.alpha = alpha; P.beta = beta;
     P.rows = rows; P.cols = cols;
     P.nbytes = (nbits + 7) >> 3;
@@ -135,6 +140,31 @@ inline bool describe(Packed& P, const uint8_t* packed, const float* alpha, const
     P.levels = levels; P.bits = bits;
     P.small = n < ((int64_t)1 << 32);
     return true;
+}
+
+// The test hook q??_set_grid_cap of every library: blocks per launch, 0 = none.  One variable per library, since each library
+// is one translation unit.
+int g_grid_cap = 0;
+
+inline int set_grid_cap(int blocks) {
+    const int prev = g_grid_cap;
+    g_grid_cap = blocks >= 1 ? blocks : 0;
+    return prev;
+}
+
+// The blocks of a launch: what the problem asks for, at most the kernel's own cap and the test hook's, at least one.
+inline int capped(int64_t blocks, int64_t own_cap) {
+    if (blocks > own_cap) blocks = own_cap;
+    if (g_grid_cap >= 1 && blocks > g_grid_cap) blocks = g_grid_cap;
+    return blocks < 1 ? 1 : (int)blocks;
+}
+
+// q??_error_string of every library; invalid_argument: its Q??_ERR_INVALID_ARGUMENT.
+inline const char* error_string(int code, int invalid_argument) {
+    if (code == 0) return "success";
+    if (code == invalid_argument) return "invalid argument";
+    if (code > 0) return hipGetErrorString((hipError_t)code);
+    return "unknown error";
 }
 
 }  // namespace

@@ -1,8 +1,10 @@
 // qdm_linear.hip -- libqd_infer_mm.so: the Linear layer of include/qd_infer.h for MANY rows of x (include/qd_infer_mm.h),
-// gfx950.  The one kernel of this project that uses matrix instructions: a weight decoded once from its bits / 8 bytes
-// feeds up to 64 rows of x through v_mfma_f32_16x16x4_f32 -- fp32 in, fp32 accumulate, so every weight is bit for bit the
-// value of the header and neither x nor y is rounded to a narrower type.  Nothing of libqd_hip.so or libqd_infer.so is
-// linked in; the decode is the shared one of qdi_packed.h.
+// gfx950.  A weight decoded once from its bits / 8 bytes feeds up to 64 rows of x through v_mfma_f32_16x16x4_f32 -- fp32 in,
+// fp32 accumulate, so every weight is bit for bit the value of the header and neither x nor y is rounded to a narrower type.
+// Nothing of libqd_hip.so or libqd_infer.so is linked in; the decode is the shared one of qdi_packed.h; the slabs, the LDS
+// layout, the register double buffer and the order of an output element are described in qdi_mm.h, which holds the pieces of the K
+// walk this kernel shares with k_lstm_cell_mm and k_conv2d_mm.  The staging of x and the slab loop are written out here (and, the
+// same text, in k_lstm_cell_mm): qdi_mm.h says why.
 //
 // k_linear_mm, one block of 256 threads (4 waves) per tile of 16 weight rows (N) x up to 64 rows of x (an "m-chunk"):
 //   split     tiles = N-tiles x m-chunks, m-chunk fastest (the blocks that decode the same 16 weight rows run next to each
@@ -15,22 +17,9 @@
 //             been freed of their waits.  Tiles of 16 rows give 4 x the blocks, a quarter of the decode per thread and slab
 //             (ONE group of four), and registers for four and more blocks per CU; the price is that the x slab is staged once per 16
 //             weight rows instead of once per 64 (from L2: x is m K 4 bytes).
-//   K slabs   64 columns at a time through LDS: ws[16][68] (weights, decoded ONCE per tile and slab: thread t decodes the group
-//             of four [4 (t % 16), + 4) of row t / 16: one bucket search per thread and tile, steps of 64 elements from there)
-//             and xs[64][68] (thread t: the 16 columns [16 (t % 4), + 16) of row t / 4, 16-byte global loads at any 4-byte phase,
-//             64 contiguous bytes of a row per thread; the 16 lanes of a b128 LDS write cover all 64 banks).  The second
-//             buffer is REGISTERS, not LDS: slab s + 1's loads (two stream words, alpha, beta, x: 20 VGPRs) are issued before
-//             slab s's MFMAs and become LDS contents after them (fetch4 / finish4), with two barriers per slab.  fetch() holds
-//             loads ONLY -- no instruction that consumes a loaded value -- so none of them is waited for before the MFMAs.
 //   operands  A = x (a lane gives x[i0 + 16 w + l % 16][k]), B = W^T (w[r0 + l % 16][k]), so D[i][j] has j = l % 16 along N: the
 //             16 lanes of a row group store 64 contiguous bytes of one row of y.
-//   LDS reads a row stride of 68 floats; lane l reads the FOUR floats [l % 16][16 q + 4 (l / 16), + 4) of a 16-column
-//             group as one ds_read_b128 and feeds them to four MFMAs: MFMA jj of group q multiplies the columns
-//             16 q + jj + {0, 4, 8, 12}.  68 r mod 64 = 4 r: the 16 lanes a b128 read serves per cycle cover all 64 banks.
-//   order     of an output element: slabs front to back, inside a slab the 16-column groups front to back, inside a group
-//             jj = 0 .. 3, each MFMA adding its four products to the running accumulator; a last slab of fewer than 64
-//             columns runs only the groups that hold a column.  A function of cols alone.
-#include "qdi_packed.h"       // Packed, describe, stream_bits, divmod, build_quotients, fetch4 / finish4: shared with qdi_layers.hip
+#include "qdi_mm.h"           // the shared pieces of the K walk; through it qdi_packed.h: Packed, describe, the decode, the host helpers
 
 #include "../../../include/qd_infer_mm.h"
 
@@ -38,17 +27,7 @@ using namespace qd;
 
 namespace {
 
-constexpr int kTile = 64;              // rows of x of a chunk and columns of a slab
-constexpr int kRows = 16;              // weight rows of a tile: one MFMA block
-constexpr int kStride = 68;            // floats per LDS row: 16-byte aligned rows, conflict-free operand reads (above)
-
-int g_grid_cap = 0;                    // qdm_set_grid_cap: 0 = none
-
-int capped(int64_t blocks, int64_t own_cap) {
-    if (blocks > own_cap) blocks = own_cap;
-    if (g_grid_cap >= 1 && blocks > g_grid_cap) blocks = g_grid_cap;
-    return blocks < 1 ? 1 : (int)blocks;
-}
+constexpr int kTile = 64;              // rows of x of a chunk
 
 __global__ __launch_bounds__(256) void k_linear_mm(Packed P, const float* x, int64_t m, const float* bias, float* y, int64_t m_chunks,
                                                    int64_t tiles, int64_t step_q, int64_t step_r /* 64 = step_q bucket + step_r */) {
@@ -73,8 +52,8 @@ __global__ __launch_bounds__(256) void k_linear_mm(Packed P, const float* x, int
         // in commit alike, so none of them is ever turned into an address that is read.
         int64_t e = (r0 + wr) * K + wc;                                  // its group's first element in the current slab ...
         const float* xp = x + (i0 + srow) * K + scol;
-        int64_t bkt = 0, rem = 0;                                        // ... and that element's bucket, as k_embedding finds it
-        if (wrow && wc < K) divmod(e, P.bucket, P.small, bkt, rem);
+        int64_t bkt, rem;                                                // ... and that element's bucket
+        weight_bucket(P, e, wrow && wc < K, bkt, rem);
         f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
         uint32_t lo, hi;                                                 // the next slab between its loads and its LDS writes
         float a0, b0;
@@ -95,10 +74,7 @@ __global__ __launch_bounds__(256) void k_linear_mm(Packed P, const float* x, int
         };
         // the same slab from the registers into LDS: zeros wherever nothing is to be read
         auto commit = [&](int kl) {
-            const int nw = kl - wc;                                      // columns from this group's first to the end of the row
-            float w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (wrow && nw > 0) finish4(P, qtab, lo, hi, a0, b0, e, bkt, rem, nw < 4 ? nw : 4, w);
-            *(f4*)&ws[wr * kStride + wc] = (f4){w[0], w[1], w[2], w[3]};
+            weight_commit(P, qtab, ws, wrow, kl, wr, wc, lo, hi, a0, b0, e, bkt, rem);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int nv = kl - scol - 4 * j;
@@ -121,20 +97,11 @@ __global__ __launch_bounds__(256) void k_linear_mm(Packed P, const float* x, int
             __syncthreads();
             kleft -= kTile;
             if (kleft > 0) {
-                bkt += step_q; rem += step_r;                            // 64 columns on: the bucket of the next slab's group
-                if (rem >= P.bucket) { rem -= P.bucket; ++bkt; }
-                e += kTile; xp += kTile;
+                weight_step(P, step_q, step_r, e, bkt, rem);
+                xp += kTile;
                 fetch(kleft < kTile ? (int)kleft : kTile);               // in flight during the MFMAs below
             }
-            if (mine) {
-                const int groups = (kl + 15) >> 4;
-                for (int q = 0; q < groups; ++q) {
-                    const f4 b = *(const f4*)&ws[fr * kStride + 16 * q + fk];
-                    const f4 a = *(const f4*)&xs[(16 * wave + fr) * kStride + 16 * q + fk];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], b[jj], acc, 0, 0, 0);
-                }
-            }
+            if (mine) rows_mfma<false>(ws, xs, kl, fr, fk, wave, acc);
             __syncthreads();                                             // every wave is done with this slab before the next commit
         }
 
@@ -157,25 +124,14 @@ extern "C" {
 
 int qdm_abi_version(void) { return QDM_ABI_VERSION; }
 const char* qdm_target_arch(void) { return "gfx950"; }
-
-const char* qdm_error_string(int code) {
-    if (code == 0) return "success";
-    if (code == QDM_ERR_INVALID_ARGUMENT) return "invalid argument";
-    if (code > 0) return hipGetErrorString((hipError_t)code);
-    return "unknown error";
-}
-
-int qdm_set_grid_cap(int blocks) {
-    const int prev = g_grid_cap;
-    g_grid_cap = blocks >= 1 ? blocks : 0;
-    return prev;
-}
+const char* qdm_error_string(int code) { return error_string(code, QDM_ERR_INVALID_ARGUMENT); }
+int qdm_set_grid_cap(int blocks) { return set_grid_cap(blocks); }
 
 int qdm_linear_packed_f32(const uint8_t* packed, const float* alpha, const float* beta, int64_t rows, int64_t cols, int64_t bucket,
                           int levels, int bits, const float* x, int64_t m, const float* bias, float* y, void* stream) {
     Packed P;
     if (!describe(P, packed, alpha, beta, rows, cols, bucket, levels, bits) || m < 0) return QDM_ERR_INVALID_ARGUMENT;
-    if ((((uintptr_t)x) & 3) || (((uintptr_t)bias) & 3) || (((uintptr_t)y) & 3)) return QDM_ERR_INVALID_ARGUMENT;
+    if (misaligned(x) || misaligned(bias) || misaligned(y)) return QDM_ERR_INVALID_ARGUMENT;
     int64_t t = 0;
     if (__builtin_mul_overflow(m, rows, &t) || __builtin_mul_overflow(m, cols, &t)) return QDM_ERR_INVALID_ARGUMENT;
     if (m == 0 || rows == 0) return 0;
@@ -184,7 +140,7 @@ int qdm_linear_packed_f32(const uint8_t* packed, const float* alpha, const float
     const int64_t tiles = ((rows - 1) / kRows + 1) * m_chunks;          // <= m rows: fits
     const int blocks = capped(tiles, (int64_t)device_cus() * 8);
     hipLaunchKernelGGL(k_linear_mm, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P, x, m, bias, y, m_chunks, tiles,
-                       kTile / P.bucket, kTile % P.bucket);
+                       kSlab / P.bucket, kSlab % P.bucket);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // qdr_lstm.hip -- libqd_infer_rnn.so: one LSTM step from the packed recurrent weights (include/qd_infer_rnn.h), gfx950.  Both
 // products of the step go through v_mfma_f32_16x16x4_f32 into one accumulator and the gate arithmetic is finished in the lane
 // that holds the accumulator: one launch per step, nothing of the [batch, 4 hidden] pre-activations goes to memory unless the
-// caller asks for it.  Nothing of the other libraries is linked in; the decode is the shared one of qdi_packed.h, unchanged.
+// caller asks for it.  Nothing of the other libraries is linked in; the decode is the shared one of qdi_packed.h, unchanged,
+// the weight pieces of the K walk and the MFMA loop those of qdi_mm.h.
 //
 // k_lstm_cell_mm, one block of 256 threads (4 waves) per tile of 4 hidden units x 4 gates (16 weight rows) x up to 64 batch rows:
 //   split     tiles = unit-tiles x batch-chunks, chunk fastest (the blocks that decode the same 16 weight rows run next to each
@@ -19,11 +20,10 @@
 //             registers (fetch4 before the MFMAs, finish4 after them), two barriers per slab.  Each part has its own ragged last
 //             slab; a slab never straddles the parts.  The description, the quotient table, the bucket state and the activation
 //             pointer switch once per tile, between the parts; the accumulator runs through.
-//   LDS reads as k_linear_mm: row stride 68 floats, lane l reads the four floats [l % 16][16 q + 4 (l / 16), + 4) of a 16-column
-//             group as one ds_read_b128 and feeds them to four MFMAs (columns 16 q + jj + {0, 4, 8, 12}); conflict-free.
+//   LDS reads rows_mfma of qdi_mm.h (there: the slab layout, the bucket search and step, the weight commit), A = W.
 //   order     of a pre-activation: the parts in turn, slabs front to back, groups front to back, jj = 0 .. 3: a function of
 //             input and hidden alone.
-#include "qdi_packed.h"       // Packed, describe, divmod, build_quotients, fetch4 / finish4: shared with the other inference libraries
+#include "qdi_mm.h"           // the pieces of the K walk; through it qdi_packed.h: Packed, describe, the decode, the host helpers
 
 #include "../../../include/qd_infer_rnn.h"
 
@@ -31,17 +31,8 @@ using namespace qd;
 
 namespace {
 
-constexpr int kTile = 64;              // batch rows of a chunk and columns of a slab
-constexpr int kUnits = 4;              // hidden units of a tile: 4 units x 4 gates = 16 weight rows, one MFMA block
-constexpr int kStride = 68;            // floats per LDS row: 16-byte aligned rows, conflict-free operand reads
-
-int g_grid_cap = 0;                    // qdr_set_grid_cap: 0 = none
-
-int capped(int64_t blocks, int64_t own_cap) {
-    if (blocks > own_cap) blocks = own_cap;
-    if (g_grid_cap >= 1 && blocks > g_grid_cap) blocks = g_grid_cap;
-    return blocks < 1 ? 1 : (int)blocks;
-}
+constexpr int kTile = 64;              // batch rows of a chunk
+constexpr int kUnits = 4;              // hidden units of a tile: 4 units x 4 gates = kRows weight rows, one MFMA block
 
 // One of the two products of a step: the weight, the activations it multiplies ([batch][P.cols]) and 64 = step_q bucket + step_r.
 struct Part {
@@ -57,7 +48,7 @@ __global__ __launch_bounds__(256) void k_lstm_cell_mm(Parts parts, int64_t hidde
                                                       const float* bias_ih, const float* bias_hh, float* h_out, float* c_out, float* gates,
                                                       int64_t chunks, int64_t tiles) {
     __shared__ float qtabs[2][256];
-    __shared__ __attribute__((aligned(16))) float ws[4 * kUnits * kStride];
+    __shared__ __attribute__((aligned(16))) float ws[kRows * kStride];
     __shared__ __attribute__((aligned(16))) float acts[kTile * kStride];
     const bool cell = pre == nullptr;                                   // cell mode: both parts; pre mode: W_hh alone
     if (cell) build_quotients(qtabs[0], parts.part[0].P.levels);
@@ -86,8 +77,8 @@ __global__ __launch_bounds__(256) void k_lstm_cell_mm(Parts parts, int64_t hidde
             const int64_t K = P.cols;
             int64_t e = wrow_index * K + wc;                              // its group's first element in the current slab ...
             const float* ap = pt.act + (i0 + srow) * K + scol;
-            int64_t bkt = 0, rem = 0;                                     // ... and that element's bucket
-            if (wrow && wc < K) divmod(e, P.bucket, P.small, bkt, rem);
+            int64_t bkt, rem;                                             // ... and that element's bucket
+            weight_bucket(P, e, wrow && wc < K, bkt, rem);
             uint32_t lo, hi;                                              // the next slab between its loads and its LDS writes
             float a0, b0;
             f4 an[4];
@@ -105,10 +96,7 @@ __global__ __launch_bounds__(256) void k_lstm_cell_mm(Parts parts, int64_t hidde
             };
             // the same slab from the registers into LDS: zeros wherever nothing is to be read
             auto commit = [&](int kl) {
-                const int nw = kl - wc;                                   // columns from this group's first to the end of the row
-                float w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (wrow && nw > 0) finish4(P, qtab, lo, hi, a0, b0, e, bkt, rem, nw < 4 ? nw : 4, w);
-                *(f4*)&ws[wr * kStride + wc] = (f4){w[0], w[1], w[2], w[3]};
+                weight_commit(P, qtab, ws, wrow, kl, wr, wc, lo, hi, a0, b0, e, bkt, rem);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int nv = kl - scol - 4 * j;
@@ -124,27 +112,18 @@ __global__ __launch_bounds__(256) void k_lstm_cell_mm(Parts parts, int64_t hidde
             };
 
             int64_t kleft = K;                                            // columns from the current slab's first to the end of the row
-            if (kleft > 0) fetch(kleft < kTile ? (int)kleft : kTile);
+            if (kleft > 0) fetch(kleft < kSlab ? (int)kleft : kSlab);
             while (kleft > 0) {
-                const int kl = kleft < kTile ? (int)kleft : kTile;
+                const int kl = kleft < kSlab ? (int)kleft : kSlab;
                 commit(kl);
                 __syncthreads();
-                kleft -= kTile;
+                kleft -= kSlab;
                 if (kleft > 0) {
-                    bkt += pt.step_q; rem += pt.step_r;                   // 64 columns on: the bucket of the next slab's group
-                    if (rem >= P.bucket) { rem -= P.bucket; ++bkt; }
-                    e += kTile; ap += kTile;
-                    fetch(kleft < kTile ? (int)kleft : kTile);            // in flight during the MFMAs below
+                    weight_step(P, pt.step_q, pt.step_r, e, bkt, rem);
+                    ap += kSlab;
+                    fetch(kleft < kSlab ? (int)kleft : kSlab);            // in flight during the MFMAs below
                 }
-                if (mine) {
-                    const int groups = (kl + 15) >> 4;
-                    for (int q = 0; q < groups; ++q) {
-                        const f4 a = *(const f4*)&ws[fr * kStride + 16 * q + fk];
-                        const f4 b = *(const f4*)&acts[(16 * wave + fr) * kStride + 16 * q + fk];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jj], b[jj], acc, 0, 0, 0);
-                    }
-                }
+                if (mine) rows_mfma<true>(ws, acts, kl, fr, fk, wave, acc);
                 __syncthreads();                                          // every wave is done with this slab before the next commit (of either part)
             }
         }
@@ -174,8 +153,6 @@ __global__ __launch_bounds__(256) void k_lstm_cell_mm(Parts parts, int64_t hidde
     }
 }
 
-bool misaligned(const void* p) { return (((uintptr_t)p) & 3) != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -183,18 +160,8 @@ extern "C" {
 int qdr_abi_version(void) { return QDR_ABI_VERSION; }
 const char* qdr_target_arch(void) { return "gfx950"; }
 
-const char* qdr_error_string(int code) {
-    if (code == 0) return "success";
-    if (code == QDR_ERR_INVALID_ARGUMENT) return "invalid argument";
-    if (code > 0) return hipGetErrorString((hipError_t)code);
-    return "unknown error";
-}
-
-int qdr_set_grid_cap(int blocks) {
-    const int prev = g_grid_cap;
-    g_grid_cap = blocks >= 1 ? blocks : 0;
-    return prev;
-}
+const char* qdr_error_string(int code) { return error_string(code, QDR_ERR_INVALID_ARGUMENT); }
+int qdr_set_grid_cap(int blocks) { return set_grid_cap(blocks); }
 
 int qdr_lstm_cell_packed_f32(const uint8_t* packed_ih, const float* alpha_ih, const float* beta_ih, int64_t bucket_ih, int levels_ih, int bits_ih,
                              const uint8_t* packed_hh, const float* alpha_hh, const float* beta_hh, int64_t bucket_hh, int levels_hh, int bits_hh,
@@ -216,8 +183,8 @@ int qdr_lstm_cell_packed_f32(const uint8_t* packed_ih, const float* alpha_ih, co
     if (!x && !pre) return QDR_ERR_INVALID_ARGUMENT;
     if (!h || !c || !h_out || !c_out || h_out == h || !packed_hh || !alpha_hh || !beta_hh) return QDR_ERR_INVALID_ARGUMENT;
     if (cell && input > 0 && (!packed_ih || !alpha_ih || !beta_ih)) return QDR_ERR_INVALID_ARGUMENT;
-    hh.act = h; hh.step_q = kTile / hh.P.bucket; hh.step_r = kTile % hh.P.bucket;
-    if (cell) { ih.act = x; ih.step_q = kTile / ih.P.bucket; ih.step_r = kTile % ih.P.bucket; }
+    hh.act = h; hh.step_q = kSlab / hh.P.bucket; hh.step_r = kSlab % hh.P.bucket;
+    if (cell) { ih.act = x; ih.step_q = kSlab / ih.P.bucket; ih.step_r = kSlab % ih.P.bucket; }
     const int64_t chunks = (batch - 1) / kTile + 1;
     const int64_t tiles = ((hidden - 1) / kUnits + 1) * chunks;         // <= batch hidden: fits
     const int blocks = capped(tiles, (int64_t)device_cus() * 8);

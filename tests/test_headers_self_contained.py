@@ -1,4 +1,4 @@
-"""Every header under csrc/ includes what it uses: a translation unit that includes ONLY that header passes hipcc's syntax check
+"""Every header under csrc/ and csrc/infer/ includes what it uses: a translation unit that includes ONLY that header passes hipcc's syntax check
 for gfx950 with the build's own compile flags.  No GPU, nothing is launched; skipped where hipcc is not installed.  The pin of
 the include hygiene of the bucket-transform headers (qd_launch.h, qd_points.h, qd_element.h, qd_bucket_*_kernels.h,
 qd_single_kernels.h, qd_transform.h): a unit may take the launch helpers without the kernels, or one kernel family without the
@@ -8,15 +8,16 @@ import subprocess
 
 import pytest
 
-from quantized_distillation_amd import _lib
+from quantized_distillation_amd import _infer, _lib
 from quantized_distillation_amd import build as qb
 
 HEADERS = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith('.h'))
+HEADERS += sorted(os.path.join('infer', f) for f in os.listdir(_infer.CSRC) if f.endswith('.h'))       # the inference libraries' own
 
 
 def test_the_list_has_the_headers_of_the_split():
     assert {'qd_common.h', 'qd_plan.h', 'qd_launch.h', 'qd_points.h', 'qd_element.h', 'qd_single_kernels.h',
-            'qd_transform.h'} <= set(HEADERS)
+            'qd_transform.h', os.path.join('infer', 'qdi_packed.h'), os.path.join('infer', 'qdi_mm.h')} <= set(HEADERS)
 
 
 @pytest.mark.parametrize('header', HEADERS)

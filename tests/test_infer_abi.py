@@ -5,18 +5,16 @@ library's header stays what it was: no qdi_ symbol in include/qd_hip.h, no entry
 import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 import torch
 from torch import nn
 
+import infer_abi_cases as A
 from quantized_distillation_amd import _infer, _lib, codec, packed_layers
 from quantized_distillation_amd import build as qb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'qd_infer.h')
 
 
 @pytest.fixture(scope='module')
@@ -25,19 +23,8 @@ def lib():
     return _infer.load()
 
 
-def header_symbols():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(qdi_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_header_binding_and_exports_agree(lib):
-    syms = header_symbols()
-    assert syms == sorted(_infer.SIGNATURES) and len(syms) == 6
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _infer.LIB_PATH], text=True)
-    assert sorted(set(re.findall(r' T (qdi?_[a-z0-9_]+)', out))) == syms          # and nothing named qd_: no entry point of qd_hip.h
-    assert int(re.search(r'#define QDI_ABI_VERSION (\d+)', open(HEADER).read()).group(1)) == _infer.ABI_VERSION == lib.qdi_abi_version() == 1
-    assert lib.qdi_target_arch() == b'gfx950'
-    assert lib.qdi_error_string(0) == b'success' and b'invalid' in lib.qdi_error_string(-1)
+    A.check_header_binding_and_exports_agree(lib, _infer, 'qd_infer.h', 'qdi', 6)    # and nothing named qd_: no entry point of qd_hip.h
 
 
 def test_the_training_library_is_untouched():
@@ -53,16 +40,7 @@ def test_one_device_target(lib):
 
 
 def test_no_kernel_uses_scratch_or_spills(lib):
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import kernel_meta
-    ks = kernel_meta.kernels(_infer.LIB_PATH)
-    names = ' '.join(kernel_meta.demangle([k['name'] for k in ks]).values())
-    assert len(ks) == 5 and 'k_embedding' in names and all('k_linear<%d>' % mt in names for mt in (1, 2, 4, 8)), names
-    bad = [(k['name'], k.get('private_segment_fixed_size', 0), k.get('vgpr_spill_count', 0), k.get('sgpr_spill_count', 0)) for k in ks
-           if k.get('private_segment_fixed_size', 0) != 0 or k.get('vgpr_spill_count', 0) != 0 or k.get('sgpr_spill_count', 0) != 0
-           or k.get('uses_dynamic_stack') == 'true']
-    assert not bad, bad
-    assert all(k['vgpr_count'] <= 128 for k in ks), [(k['name'], k['vgpr_count']) for k in ks]
+    A.check_no_kernel_uses_scratch_or_spills(_infer, ['k_embedding'] + ['k_linear<%d>' % mt for mt in (1, 2, 4, 8)], vgpr_limit=128)
 
 
 def test_grid_cap_hook(lib):

@@ -1,21 +1,13 @@
 """libqd_infer_mm.so (include/qd_infer_mm.h: the batched Linear layer from packed weights on fp32 MFMA) builds for gfx950
 without a GPU, exports exactly the header's symbols, keeps its kernel free of scratch and spills and refuses bad arguments
 before it touches a device; PackedLinear validates batched_from before any launch."""
-import os
-import re
-import subprocess
-import sys
-
 import pytest
 import torch
 from torch import nn
 
+import infer_abi_cases as A
 from quantized_distillation_amd import _infer_mm, codec, packed_layers
 from quantized_distillation_amd import build as qb
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'qd_infer_mm.h')
-
 
 @pytest.fixture(scope='module')
 def lib():
@@ -24,27 +16,12 @@ def lib():
 
 
 def test_header_binding_and_exports_agree(lib):
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    syms = sorted(set(re.findall(r'\b(qdm_[a-z0-9_]+)\s*\(', text)))
-    assert syms == sorted(_infer_mm.SIGNATURES) and len(syms) == 5
-    out = subprocess.check_output(['nm', '-D', '--defined-only', _infer_mm.LIB_PATH], text=True)
-    assert sorted(set(re.findall(r' T (qd[a-z]?_[a-z0-9_]+)', out))) == syms                  # and nothing named qd_ or qdi_
-    assert int(re.search(r'#define QDM_ABI_VERSION (\d+)', open(HEADER).read()).group(1)) == _infer_mm.ABI_VERSION == lib.qdm_abi_version() == 1
-    assert lib.qdm_target_arch() == b'gfx950'
-    assert lib.qdm_error_string(0) == b'success' and b'invalid' in lib.qdm_error_string(-1)
+    A.check_header_binding_and_exports_agree(lib, _infer_mm, 'qd_infer_mm.h', 'qdm', 5)                 # and no symbol of another library's header
     assert not set(qb.INFER_MM_SOURCES) & (set(qb.SOURCES) | set(qb.INFER_SOURCES))
-    blob = open(_infer_mm.LIB_PATH, 'rb').read()
-    assert set(re.findall(rb'hipv4-amdgcn-amd-amdhsa--(gfx[0-9a-z]+)', blob)) == {b'gfx950'}
 
 
 def test_the_kernel_uses_no_scratch_and_spills_nothing(lib):
-    sys.path.insert(0, os.path.join(ROOT, 'tools'))
-    import kernel_meta
-    ks = kernel_meta.kernels(_infer_mm.LIB_PATH)
-    assert len(ks) == 1 and 'k_linear_mm' in ks[0]['name']
-    k = ks[0]
-    assert (k.get('private_segment_fixed_size', 0), k.get('vgpr_spill_count', 0), k.get('sgpr_spill_count', 0)) == (0, 0, 0), k
-    assert k.get('uses_dynamic_stack') != 'true' and k['group_segment_fixed_size'] <= 64 * 1024, k
+    A.check_no_kernel_uses_scratch_or_spills(_infer_mm, ['k_linear_mm'], lds_limit=64 * 1024)
 
 
 def test_refusals_and_empty_calls_without_a_device(lib):
