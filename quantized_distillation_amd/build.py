@@ -182,8 +182,11 @@ INFER_LIBRARIES = [
     # of which the packed forms could pair a handful of multiplies and adds at the most, and the header words every operation
     # as one scalar fp32 operation.  The build with the forms on was not made.
     ('libqd_infer_rnn.so', ['qdr_lstm.hip'], 'qd_infer_rnn.h', INFER_MM_FLAGS, '_infer_rnn'),
+    # One GRU step, the two products on fp32 MFMA as two sums and the gate arithmetic in the same launch.  INFER_MM_FLAGS for the
+    # reason of the row above: the header words r, z, n and h' one scalar fp32 operation at a time.
+    ('libqd_infer_gru.so', ['qdg_gru.hip'], 'qd_infer_gru.h', INFER_MM_FLAGS, '_infer_gru'),
 ]
-INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES = (row[1] for row in INFER_LIBRARIES)
+INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES, INFER_GRU_SOURCES = (row[1] for row in INFER_LIBRARIES)
 
 
 def build_infer_library(library, force=False, verbose=False):
@@ -222,6 +225,10 @@ def build_infer_conv(force=False, verbose=False):
 
 def build_infer_rnn(force=False, verbose=False):
     return build_infer_library('libqd_infer_rnn.so', force, verbose)
+
+
+def build_infer_gru(force=False, verbose=False):
+    return build_infer_library('libqd_infer_gru.so', force, verbose)
 
 
 if __name__ == '__main__':

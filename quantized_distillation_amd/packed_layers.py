@@ -1,11 +1,12 @@
-"""nn.Linear, nn.Embedding, nn.Conv2d, nn.LSTMCell and nn.LSTM that run straight from the packed level indices of a quantized
-weight (libqd_infer.so, include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h; convolutions
-libqd_infer_conv.so, include/qd_infer_conv.h; LSTM steps libqd_infer_rnn.so, include/qd_infer_rnn.h): a layer keeps `bits` bits per
+"""nn.Linear, nn.Embedding, nn.Conv2d, nn.LSTMCell, nn.LSTM, nn.GRUCell and nn.GRU that run straight from the packed level indices
+of a quantized weight (libqd_infer.so, include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h;
+convolutions libqd_infer_conv.so, include/qd_infer_conv.h; LSTM steps libqd_infer_rnn.so, include/qd_infer_rnn.h; GRU steps
+libqd_infer_gru.so, include/qd_infer_gru.h): a layer keeps `bits` bits per
 weight + (alpha, beta) per bucket on the device and never holds the fp32 tensor.  The format is codec.pack_uniform's for the
 2-D weight; the value of a weight is bit for bit what PackedUniform.unpack() gives.
 
 Inference only: the outputs carry no grad_fn.  To train or fine-tune, take `unpack()` -- an ordinary nn.Linear /
-nn.Embedding / nn.Conv2d / nn.LSTMCell / nn.LSTM with the fake-quantized fp32 weights.  HIP device only: there is no CPU path.
+nn.Embedding / nn.Conv2d / nn.LSTMCell / nn.LSTM / nn.GRUCell / nn.GRU with the fake-quantized fp32 weights.  HIP device only: there is no CPU path.
 """
 import collections.abc
 
@@ -332,7 +333,7 @@ def _check_rnn_tensor(t, what, shape=None):
 
 
 def _check_rnn_call(module, tensors):
-    """Devices and grad mode of a PackedLSTMCell / PackedLSTM call: everything on the weight's HIP device, nothing to differentiate."""
+    """Devices and grad mode of a PackedLSTMCell / PackedLSTM / PackedGRUCell / PackedGRU call: everything on the weight's HIP device, nothing to differentiate."""
     name = type(module).__name__
     _require_device(module._device_of(), name)
     for t in tensors:
@@ -344,29 +345,8 @@ def _check_rnn_call(module, tensors):
                                'or train with unpack(), the torch module of the fake-quantized weights' % name)
 
 
-class PackedLSTMCell(nn.Module):
-    """nn.LSTMCell with W_ih [4 hidden, input] and W_hh [4 hidden, hidden] read from their packed level indices, each packed as a
-    tensor of its own (qdr_lstm_cell_packed_f32, libqd_infer_rnn.so, loaded on first use: both products on fp32 MFMA into one
-    accumulator and the gate arithmetic in the same launch).  forward(x, (h, c)) -> (h', c'); without a state, zeros."""
-
-    def __init__(self, packed_ih, packed_hh, bias_ih=None, bias_hh=None):
-        super().__init__()
-        self.ih = _PackedModule(packed_ih, bias_ih)
-        self.hh = _PackedModule(packed_hh, bias_hh)
-        self.input_size, self.hidden_size = self.ih.cols, self.hh.cols
-        if self.hh.rows != 4 * self.hidden_size or self.ih.rows != self.hh.rows:
-            raise ValueError('the packed weights must be [4 hidden, input] and [4 hidden, hidden], got [%d, %d] and [%d, %d]'
-                             % (self.ih.rows, self.ih.cols, self.hh.rows, self.hh.cols))
-        if self.ih.packed.device != self.hh.packed.device:
-            raise ValueError('W_ih lives on %s, W_hh on %s' % (self.ih.packed.device, self.hh.packed.device))
-
-    @classmethod
-    def from_lstm_cell(cls, cell, s, bucket_size=256, bits=None):
-        """Quantize weight_ih and weight_hh of an nn.LSTMCell, each as its own tensor, with `s` levels per bucket."""
-        if not isinstance(cell, nn.LSTMCell):
-            raise TypeError('from_lstm_cell takes an nn.LSTMCell, got %r' % type(cell))
-        return cls._from_weights(cell.weight_ih, cell.weight_hh, cell.bias_ih if cell.bias else None, cell.bias_hh if cell.bias else None,
-                                 s, bucket_size, bits, 'PackedLSTMCell.from_lstm_cell')
+class _PackedRecurrentCell(nn.Module):
+    """What PackedLSTMCell and PackedGRUCell share: two packed weights `ih` and `hh` (each a _PackedModule with its bias)."""
 
     @classmethod
     def _from_weights(cls, w_ih, w_hh, b_ih, b_hh, s, bucket_size, bits, what):
@@ -391,6 +371,50 @@ class PackedLSTMCell(nn.Module):
 
     def _weight_args(self, part):
         return (part.packed.data_ptr(), part.alpha.data_ptr(), part.beta.data_ptr(), part.bucket_size or 0, part.s, part.bits)
+
+
+class _PackedRecurrent(nn.Module):
+    """What PackedLSTM and PackedGRU share: `cells`, one packed cell per layer and direction."""
+
+    @property
+    def nbytes(self):
+        return sum(cl.nbytes for cl in self.cells)
+
+    @property
+    def fp32_nbytes(self):
+        return sum(cl.fp32_nbytes for cl in self.cells)
+
+    def extra_repr(self):
+        return '%d, %d, num_layers=%d, bidirectional=%s, batch_first=%s' % (self.input_size, self.hidden_size, self.num_layers,
+                                                                            self.bidirectional, self.batch_first)
+
+    def _device_of(self):
+        return self.cells[0]._device_of()
+
+
+class PackedLSTMCell(_PackedRecurrentCell):
+    """nn.LSTMCell with W_ih [4 hidden, input] and W_hh [4 hidden, hidden] read from their packed level indices, each packed as a
+    tensor of its own (qdr_lstm_cell_packed_f32, libqd_infer_rnn.so, loaded on first use: both products on fp32 MFMA into one
+    accumulator and the gate arithmetic in the same launch).  forward(x, (h, c)) -> (h', c'); without a state, zeros."""
+
+    def __init__(self, packed_ih, packed_hh, bias_ih=None, bias_hh=None):
+        super().__init__()
+        self.ih = _PackedModule(packed_ih, bias_ih)
+        self.hh = _PackedModule(packed_hh, bias_hh)
+        self.input_size, self.hidden_size = self.ih.cols, self.hh.cols
+        if self.hh.rows != 4 * self.hidden_size or self.ih.rows != self.hh.rows:
+            raise ValueError('the packed weights must be [4 hidden, input] and [4 hidden, hidden], got [%d, %d] and [%d, %d]'
+                             % (self.ih.rows, self.ih.cols, self.hh.rows, self.hh.cols))
+        if self.ih.packed.device != self.hh.packed.device:
+            raise ValueError('W_ih lives on %s, W_hh on %s' % (self.ih.packed.device, self.hh.packed.device))
+
+    @classmethod
+    def from_lstm_cell(cls, cell, s, bucket_size=256, bits=None):
+        """Quantize weight_ih and weight_hh of an nn.LSTMCell, each as its own tensor, with `s` levels per bucket."""
+        if not isinstance(cell, nn.LSTMCell):
+            raise TypeError('from_lstm_cell takes an nn.LSTMCell, got %r' % type(cell))
+        return cls._from_weights(cell.weight_ih, cell.weight_hh, cell.bias_ih if cell.bias else None, cell.bias_hh if cell.bias else None,
+                                 s, bucket_size, bits, 'PackedLSTMCell.from_lstm_cell')
 
     def _step(self, x, pre, h, c, h_out, c_out):
         """One qdr_lstm_cell_packed_f32 on contiguous tensors of the current device: cell mode (x) or pre mode (pre)."""
@@ -447,7 +471,7 @@ def _check_lstm(lstm, what):
         raise ValueError('%s: an nn.LSTM with proj_size = %d has no packed form' % (what, lstm.proj_size))
 
 
-class PackedLSTM(nn.Module):
+class PackedLSTM(_PackedRecurrent):
     """nn.LSTM (any num_layers, either direction count, either batch_first; no projections, no dropout: inference) from packed
     weights.  cells: one PackedLSTMCell per layer and direction, layer-major (layer 0 forward, layer 0 reverse, layer 1 ...).
     Per layer and direction the input projection of ALL time steps is one qdm_linear_packed_f32 (libqd_infer_mm.so) with bias_ih,
@@ -484,21 +508,6 @@ class PackedLSTM(nn.Module):
                 cells.append(PackedLSTMCell._from_weights(get('weight_ih'), get('weight_hh'), get('bias_ih') if lstm.bias else None,
                                                           get('bias_hh') if lstm.bias else None, s, bucket_size, bits, 'PackedLSTM.from_lstm'))
         return cls(cells, lstm.bidirectional, lstm.batch_first)
-
-    @property
-    def nbytes(self):
-        return sum(cl.nbytes for cl in self.cells)
-
-    @property
-    def fp32_nbytes(self):
-        return sum(cl.fp32_nbytes for cl in self.cells)
-
-    def extra_repr(self):
-        return '%d, %d, num_layers=%d, bidirectional=%s, batch_first=%s' % (self.input_size, self.hidden_size, self.num_layers,
-                                                                            self.bidirectional, self.batch_first)
-
-    def _device_of(self):
-        return self.cells[0]._device_of()
 
     def forward(self, x, hx=None):
         if isinstance(x, nn.utils.rnn.PackedSequence):
@@ -574,15 +583,190 @@ class PackedLSTM(nn.Module):
         return lstm
 
 
+class PackedGRUCell(_PackedRecurrentCell):
+    """nn.GRUCell with W_ih [3 hidden, input] and W_hh [3 hidden, hidden] read from their packed level indices, each packed as a
+    tensor of its own (qdg_gru_cell_packed_f32, libqd_infer_gru.so, loaded on first use: both products on fp32 MFMA, kept as two
+    sums because the reset gate multiplies the recurrent one, and the gate arithmetic in the same launch).
+    forward(x, h=None) -> h'; without a state, zeros."""
+
+    def __init__(self, packed_ih, packed_hh, bias_ih=None, bias_hh=None):
+        super().__init__()
+        self.ih = _PackedModule(packed_ih, bias_ih)
+        self.hh = _PackedModule(packed_hh, bias_hh)
+        self.input_size, self.hidden_size = self.ih.cols, self.hh.cols
+        if self.hh.rows != 3 * self.hidden_size or self.ih.rows != self.hh.rows:
+            raise ValueError('the packed weights must be [3 hidden, input] and [3 hidden, hidden], got [%d, %d] and [%d, %d]'
+                             % (self.ih.rows, self.ih.cols, self.hh.rows, self.hh.cols))
+        if self.ih.packed.device != self.hh.packed.device:
+            raise ValueError('W_ih lives on %s, W_hh on %s' % (self.ih.packed.device, self.hh.packed.device))
+
+    @classmethod
+    def from_gru_cell(cls, cell, s, bucket_size=256, bits=None):
+        """Quantize weight_ih and weight_hh of an nn.GRUCell, each as its own tensor, with `s` levels per bucket."""
+        if not isinstance(cell, nn.GRUCell):
+            raise TypeError('from_gru_cell takes an nn.GRUCell, got %r' % type(cell))
+        return cls._from_weights(cell.weight_ih, cell.weight_hh, cell.bias_ih if cell.bias else None, cell.bias_hh if cell.bias else None,
+                                 s, bucket_size, bits, 'PackedGRUCell.from_gru_cell')
+
+    def _step(self, x, pre, h, h_out):
+        """One qdg_gru_cell_packed_f32 on contiguous tensors of the current device: cell mode (x) or pre mode (pre)."""
+        from . import _infer_gru                                         # libqd_infer_gru.so: on first use only
+        ptr = lambda t: None if t is None else t.data_ptr()              # noqa: E731
+        ih = self._weight_args(self.ih) if pre is None else (None, None, None, 0, 0, 0)
+        _infer_gru.check(_infer_gru.load().qdg_gru_cell_packed_f32(
+            *ih, *self._weight_args(self.hh), self.hidden_size, self.input_size, ptr(x), ptr(pre), h.data_ptr(), h.shape[0],
+            ptr(self.ih.bias) if pre is None else None, ptr(self.hh.bias), h_out.data_ptr(), None, _lib.stream_ptr()))
+
+    def forward(self, x, h=None):
+        _check_rnn_tensor(x, 'x')
+        if x.dim() not in (1, 2) or x.shape[-1] != self.input_size:
+            raise ValueError('x must be [batch, %d] or [%d], got shape %s' % (self.input_size, self.input_size, tuple(x.shape)))
+        lead = tuple(x.shape[:-1])
+        if h is not None:
+            _check_rnn_tensor(h, 'h', lead + (self.hidden_size,))
+        _check_rnn_call(self, (x,) if h is None else (x, h))
+        if _lib.on_other_device(x):
+            with torch.cuda.device(x.device):
+                return self.forward(x, h)
+        batch = x.shape[0] if x.dim() == 2 else 1
+        xc = x.detach().contiguous().view(batch, self.input_size)
+        if h is None:
+            hc = torch.zeros(batch, self.hidden_size, dtype=torch.float32, device=x.device)
+        else:
+            hc = h.detach().contiguous().view(batch, self.hidden_size)
+        h_out = torch.empty_like(hc)
+        self._step(xc, None, hc, h_out)
+        return h_out.view(lead + (self.hidden_size,))
+
+    def unpack(self):
+        """An ordinary nn.GRUCell holding the fake-quantized fp32 weights (and the biases)."""
+        w_ih, w_hh = self.ih._weight(), self.hh._weight()
+        if (self.ih.bias is None) != (self.hh.bias is None):
+            raise ValueError('an nn.GRUCell has both biases or none; this cell has one')
+        cell = nn.GRUCell(self.input_size, self.hidden_size, bias=self.hh.bias is not None, device=w_hh.device)
+        with torch.no_grad():
+            cell.weight_ih.copy_(w_ih)
+            cell.weight_hh.copy_(w_hh)
+            if self.hh.bias is not None:
+                cell.bias_ih.copy_(self.ih.bias)
+                cell.bias_hh.copy_(self.hh.bias)
+        return cell
+
+
+class PackedGRU(_PackedRecurrent):
+    """nn.GRU (any num_layers, either direction count, either batch_first; no dropout: inference) from packed weights.  cells: one
+    PackedGRUCell per layer and direction, layer-major (layer 0 forward, layer 0 reverse, layer 1 ...).  Per layer and direction
+    the input projection of ALL time steps is one qdm_linear_packed_f32 (libqd_infer_mm.so) with bias_ih, then T launches of
+    qdg_gru_cell_packed_f32 in pre mode: step t reads h of the step before from the layer's output and writes its own there.  The
+    reverse direction is the same kernel walked from T - 1 down.  A bidirectional layer writes each direction's steps to a buffer
+    of its own and concatenates them once per layer.  forward(x, hx=None) -> (output, h_n) in nn.GRU's shapes."""
+
+    def __init__(self, cells, bidirectional=False, batch_first=False):
+        super().__init__()
+        cells = list(cells)
+        dirs = 2 if bidirectional else 1
+        if not cells or len(cells) % dirs or any(not isinstance(cl, PackedGRUCell) for cl in cells):
+            raise ValueError('cells must be a non-empty list of PackedGRUCell, one per layer and direction')
+        self.bidirectional, self.batch_first = bool(bidirectional), bool(batch_first)
+        self.num_layers = len(cells) // dirs
+        self.input_size, self.hidden_size = cells[0].input_size, cells[0].hidden_size
+        for k, cl in enumerate(cells):
+            want = self.input_size if k < dirs else dirs * self.hidden_size
+            if cl.hidden_size != self.hidden_size or cl.input_size != want:
+                raise ValueError('cell %d must be (input %d, hidden %d), got (%d, %d)' % (k, want, self.hidden_size, cl.input_size, cl.hidden_size))
+            if cl._device_of().device != cells[0]._device_of().device:
+                raise ValueError('the cells live on different devices')
+        self.cells = nn.ModuleList(cells)
+
+    @classmethod
+    def from_gru(cls, gru, s, bucket_size=256, bits=None):
+        """Quantize every weight_ih_l* / weight_hh_l* of an nn.GRU, each as its own tensor, with `s` levels per bucket."""
+        if not isinstance(gru, nn.GRU):
+            raise TypeError('PackedGRU.from_gru takes an nn.GRU, got %r' % type(gru))
+        cells = []
+        for layer in range(gru.num_layers):
+            for sfx in ('', '_reverse')[:2 if gru.bidirectional else 1]:
+                get = lambda name: getattr(gru, '%s_l%d%s' % (name, layer, sfx))            # noqa: E731
+                cells.append(PackedGRUCell._from_weights(get('weight_ih'), get('weight_hh'), get('bias_ih') if gru.bias else None,
+                                                         get('bias_hh') if gru.bias else None, s, bucket_size, bits, 'PackedGRU.from_gru'))
+        return cls(cells, gru.bidirectional, gru.batch_first)
+
+    def forward(self, x, hx=None):
+        if isinstance(x, nn.utils.rnn.PackedSequence):
+            raise TypeError('PackedGRU takes a padded tensor, not a PackedSequence')
+        _check_rnn_tensor(x, 'x')
+        if x.dim() not in (2, 3) or x.shape[-1] != self.input_size:
+            raise ValueError('x must be [T, batch, %d] ([batch, T, %d] with batch_first) or [T, %d], got shape %s'
+                             % (self.input_size, self.input_size, self.input_size, tuple(x.shape)))
+        dirs = 2 if self.bidirectional else 1
+        batched = x.dim() == 3
+        seq = x if not batched else x.transpose(0, 1) if self.batch_first else x
+        T, batch = seq.shape[0], seq.shape[1] if batched else 1
+        if T == 0:
+            raise ValueError('x holds no time step')
+        state_shape = (self.num_layers * dirs,) + ((batch,) if batched else ()) + (self.hidden_size,)
+        if hx is not None:
+            _check_rnn_tensor(hx, 'h_0', state_shape)
+        _check_rnn_call(self, (x,) if hx is None else (x, hx))
+        if _lib.on_other_device(x):
+            with torch.cuda.device(x.device):
+                return self.forward(x, hx)
+        from . import _infer_mm                                          # libqd_infer_mm.so: the input projections
+        H = self.hidden_size
+        full = (self.num_layers * dirs, batch, H)
+        h0 = torch.zeros(full, dtype=torch.float32, device=x.device) if hx is None else hx.detach().contiguous().view(full)
+        h_n = torch.empty(full, dtype=torch.float32, device=x.device)
+        inp = seq.detach().contiguous().view(T, batch, self.input_size)
+        for layer in range(self.num_layers):
+            outs = []
+            for d in range(dirs):
+                k = layer * dirs + d
+                cl = self.cells[k]
+                pre = torch.empty(T, batch, 3 * H, dtype=torch.float32, device=x.device)
+                _infer_mm.check(_infer_mm.load().qdm_linear_packed_f32(
+                    *cl.ih._format_args(), inp.data_ptr(), T * batch, None if cl.ih.bias is None else cl.ih.bias.data_ptr(), pre.data_ptr(),
+                    _lib.stream_ptr()))
+                out = torch.empty(T, batch, H, dtype=torch.float32, device=x.device)
+                h = h0[k]
+                for t in (range(T - 1, -1, -1) if d else range(T)):
+                    cl._step(None, pre[t], h, out[t])
+                    h = out[t]
+                h_n[k].copy_(h)
+                outs.append(out)
+            inp = outs[0] if dirs == 1 else torch.cat(outs, dim=2)
+        if not batched:
+            return inp.view(T, dirs * H), h_n.view(state_shape)
+        return (inp.transpose(0, 1) if self.batch_first else inp), h_n
+
+    def unpack(self):
+        """An ordinary nn.GRU holding the fake-quantized fp32 weights (and the biases)."""
+        biased = self.cells[0].hh.bias is not None
+        if any((cl.ih.bias is not None) != biased or (cl.hh.bias is not None) != biased for cl in self.cells):
+            raise ValueError('an nn.GRU has every bias or none; these cells differ')
+        gru = nn.GRU(self.input_size, self.hidden_size, self.num_layers, bias=biased, batch_first=self.batch_first,
+                     bidirectional=self.bidirectional, device=self._device_of().device)
+        dirs = 2 if self.bidirectional else 1
+        with torch.no_grad():
+            for k, cl in enumerate(self.cells):
+                sfx = '_l%d%s' % (k // dirs, '_reverse' if k % dirs else '')
+                getattr(gru, 'weight_ih' + sfx).copy_(cl.ih._weight())
+                getattr(gru, 'weight_hh' + sfx).copy_(cl.hh._weight())
+                if biased:
+                    getattr(gru, 'bias_ih' + sfx).copy_(cl.ih.bias)
+                    getattr(gru, 'bias_hh' + sfx).copy_(cl.hh.bias)
+        return gru
+
+
 def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=None, conv=False, rnn=False):
-    """Replace every nn.Linear and nn.Embedding of `model` -- with conv=True every nn.Conv2d, with rnn=True every nn.LSTM and
-    nn.LSTMCell as well (an nn.LSTM with proj_size raises before anything is changed) -- in place by its packed form.  skip: names (model.named_modules()) left as they are; s: the level count, or a mapping from module name to it (every
+    """Replace every nn.Linear and nn.Embedding of `model` -- with conv=True every nn.Conv2d, with rnn=True every nn.LSTM,
+    nn.LSTMCell, nn.GRU and nn.GRUCell as well (an nn.LSTM with proj_size raises before anything is changed) -- in place by its
+    packed form.  skip: names (model.named_modules()) left as they are; s: the level count, or a mapping from module name to it (every
     replaced module must be in it); batched_from: PackedLinear's, for every Linear replaced.  A Conv2d that has no packed form
     (groups, dilation, a padding mode) raises before anything is changed.  Returns {name: (fp32_bytes, packed_bytes)} of what
     was replaced."""
     batched_from = _batched_from(batched_from)
     skip = set(skip)
-    kinds = (nn.Linear, nn.Embedding) + ((nn.Conv2d,) if conv else ()) + ((nn.LSTM, nn.LSTMCell) if rnn else ())
+    kinds = (nn.Linear, nn.Embedding) + ((nn.Conv2d,) if conv else ()) + ((nn.LSTM, nn.LSTMCell, nn.GRU, nn.GRUCell) if rnn else ())
     todo = [(name, mod) for name, mod in model.named_modules() if isinstance(mod, kinds) and name not in skip]
     unknown = skip - {name for name, _ in model.named_modules()}
     if unknown:
@@ -611,6 +795,10 @@ def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=Non
             new = PackedLSTM.from_lstm(mod, s_i, bucket_size, bits_i)
         elif isinstance(mod, nn.LSTMCell):
             new = PackedLSTMCell.from_lstm_cell(mod, s_i, bucket_size, bits_i)
+        elif isinstance(mod, nn.GRU):
+            new = PackedGRU.from_gru(mod, s_i, bucket_size, bits_i)
+        elif isinstance(mod, nn.GRUCell):
+            new = PackedGRUCell.from_gru_cell(mod, s_i, bucket_size, bits_i)
         else:
             new = PackedEmbedding.from_embedding(mod, s_i, bucket_size, bits_i)
         parent_name, _, leaf = name.rpartition('.')
