@@ -185,8 +185,12 @@ INFER_LIBRARIES = [
     # One GRU step, the two products on fp32 MFMA as two sums and the gate arithmetic in the same launch.  INFER_MM_FLAGS for the
     # reason of the row above: the header words r, z, n and h' one scalar fp32 operation at a time.
     ('libqd_infer_gru.so', ['qdg_gru.hip'], 'qd_infer_gru.h', INFER_MM_FLAGS, '_infer_gru'),
+    # One Luong attention step: scores, softmax and context per batch row (fmaf chains and expf, no MFMA), and tanh(W_out [ctx ; x])
+    # from the packed weight on fp32 MFMA.  INFER_MM_FLAGS for the reason of the rows above: the header words every fp32 operation
+    # of both kernels as one scalar operation.
+    ('libqd_infer_attn.so', ['qda_attn.hip'], 'qd_infer_attn.h', INFER_MM_FLAGS, '_infer_attn'),
 ]
-INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES, INFER_GRU_SOURCES = (row[1] for row in INFER_LIBRARIES)
+INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES, INFER_GRU_SOURCES, INFER_ATTN_SOURCES = (row[1] for row in INFER_LIBRARIES)
 
 
 def build_infer_library(library, force=False, verbose=False):
@@ -229,6 +233,10 @@ def build_infer_rnn(force=False, verbose=False):
 
 def build_infer_gru(force=False, verbose=False):
     return build_infer_library('libqd_infer_gru.so', force, verbose)
+
+
+def build_infer_attn(force=False, verbose=False):
+    return build_infer_library('libqd_infer_attn.so', force, verbose)
 
 
 if __name__ == '__main__':

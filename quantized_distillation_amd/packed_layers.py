@@ -1,7 +1,7 @@
-"""nn.Linear, nn.Embedding, nn.Conv2d, nn.LSTMCell, nn.LSTM, nn.GRUCell and nn.GRU that run straight from the packed level indices
+"""nn.Linear, nn.Embedding, nn.Conv2d, nn.LSTMCell, nn.LSTM, nn.GRUCell, nn.GRU and a Luong global-attention step that run straight from the packed level indices
 of a quantized weight (libqd_infer.so, include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h;
 convolutions libqd_infer_conv.so, include/qd_infer_conv.h; LSTM steps libqd_infer_rnn.so, include/qd_infer_rnn.h; GRU steps
-libqd_infer_gru.so, include/qd_infer_gru.h): a layer keeps `bits` bits per
+libqd_infer_gru.so, include/qd_infer_gru.h; a global-attention step libqd_infer_attn.so, include/qd_infer_attn.h): a layer keeps `bits` bits per
 weight + (alpha, beta) per bucket on the device and never holds the fp32 tensor.  The format is codec.pack_uniform's for the
 2-D weight; the value of a weight is bit for bit what PackedUniform.unpack() gives.
 
@@ -755,6 +755,124 @@ class PackedGRU(_PackedRecurrent):
                     getattr(gru, 'bias_ih' + sfx).copy_(cl.ih.bias)
                     getattr(gru, 'bias_hh' + sfx).copy_(cl.hh.bias)
         return gru
+
+
+class PackedGlobalAttention(nn.Module):
+    """One step of Luong global attention (the `dot` and `general` scores) with the output projection W_out [dim, 2 dim], and for
+    `general` the input projection W_in [dim, dim], read from their packed level indices (libqd_infer_attn.so, include/qd_infer_attn.h,
+    loaded on first use).  forward(query [batch, dim], memory [batch, S, dim], lengths=None, keys=None) -> (attn_h [batch, dim],
+    align [batch, S]):
+
+        q      = linear_in(query) where packed_in is given (`general`: one PackedLinear call), else query (`dot`)
+        align  = softmax over s < lengths[b] of keys[b, s] . q[b], 0 from lengths[b] on      } qda_attn_context_f32, one launch;
+        ctx    = sum_s align[b, s] memory[b, s]                                               } the padding is never read
+        attn_h = tanh(W_out [ctx ; query] + bias_out)          qda_attn_out_packed_f32, one launch, no concatenation
+
+    keys defaults to memory.  A decoder that projects the memory once per sentence (keys = attn_in(memory), then `dot`, as
+    harness/models.py: Seq2SeqLSTM does) passes that projection as keys= with packed_in=None.  The concatenated operand is always
+    the original query.  lengths: an int64 [batch] tensor; a row with lengths <= 0 is NaN.
+
+    pack_modules does not build this layer -- there is no torch module to detect.  From the PackedLinear modules it leaves behind:
+    PackedGlobalAttention(m.attn_out.as_packed_uniform(), bias_out=m.attn_out.bias), with packed_in=m.attn_in.as_packed_uniform()
+    for the `general` form (a linear_in with a bias has no form here: the reference's has none).
+
+    Not offered: the `mlp` (Bahdanau) score, coverage, multi-step queries [batch, T, dim] (call once per step) and PackedSequence
+    inputs (pass the padded memory and lengths)."""
+
+    def __init__(self, packed_out, packed_in=None, bias_out=None):
+        super().__init__()
+        self.out = _PackedModule(packed_out, bias_out)
+        self.dim = self.out.rows
+        if self.out.cols != 2 * self.dim:
+            raise ValueError('packed_out must be [dim, 2 dim], got [%d, %d]' % (self.out.rows, self.out.cols))
+        self.linear_in = None
+        if packed_in is not None:
+            self.linear_in = PackedLinear(packed_in)
+            if (self.linear_in.rows, self.linear_in.cols) != (self.dim, self.dim):
+                raise ValueError('packed_in must be [%d, %d], got [%d, %d]' % (self.dim, self.dim, self.linear_in.rows, self.linear_in.cols))
+            if self.linear_in.packed.device != self.out.packed.device:
+                raise ValueError('W_in lives on %s, W_out on %s' % (self.linear_in.packed.device, self.out.packed.device))
+
+    @classmethod
+    def from_linears(cls, linear_out, linear_in=None, s=None, bucket_size=256, bits=None):
+        """Quantize the weights of the nn.Linear(2 dim, dim) behind tanh and, for `general`, of the bias-free nn.Linear(dim, dim) in
+        front of the score, each as its own tensor, with `s` levels per bucket."""
+        for lin, name in ((linear_out, 'linear_out'), (linear_in, 'linear_in')):
+            if not isinstance(lin, nn.Linear) and not (lin is None and name == 'linear_in'):
+                raise TypeError('from_linears: %s must be an nn.Linear, got %r' % (name, type(lin)))
+        if s is None:
+            raise TypeError('from_linears needs s, the number of levels')
+        if linear_in is not None and linear_in.bias is not None:
+            raise ValueError('from_linears: linear_in has a bias; the attention\'s input projection has none')
+        what = 'PackedGlobalAttention.from_linears'
+        return cls(_pack_weight(linear_out.weight, s, bucket_size, bits, what),
+                   None if linear_in is None else _pack_weight(linear_in.weight, s, bucket_size, bits, what),
+                   None if linear_out.bias is None else linear_out.bias.detach().clone())
+
+    @property
+    def nbytes(self):
+        """Bytes this layer keeps on the device: the packed weights and the fp32 bias."""
+        return self.out.nbytes + (0 if self.linear_in is None else self.linear_in.nbytes)
+
+    @property
+    def fp32_nbytes(self):
+        """Bytes of the fp32 layers it stands for."""
+        return self.out.fp32_nbytes + (0 if self.linear_in is None else self.linear_in.fp32_nbytes)
+
+    def extra_repr(self):
+        return '%d, score=%s, bias_out=%s' % (self.dim, 'dot' if self.linear_in is None else 'general', self.out.bias is not None)
+
+    def _device_of(self):
+        return self.out.packed
+
+    def forward(self, query, memory, lengths=None, keys=None):
+        if isinstance(memory, nn.utils.rnn.PackedSequence):
+            raise TypeError('PackedGlobalAttention takes the padded memory and lengths, not a PackedSequence')
+        _check_rnn_tensor(query, 'query')
+        if query.dim() != 2 or query.shape[1] != self.dim:
+            raise ValueError('query must be [batch, %d] (one step; call once per step for [batch, T, dim]), got shape %s' % (self.dim, tuple(query.shape)))
+        _check_rnn_tensor(memory, 'memory')
+        if memory.dim() != 3 or memory.shape[0] != query.shape[0] or memory.shape[2] != self.dim:
+            raise ValueError('memory must be [%d, S, %d], got shape %s' % (query.shape[0], self.dim, tuple(memory.shape)))
+        if keys is not None:
+            _check_rnn_tensor(keys, 'keys', memory.shape)
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int64:
+                raise TypeError('lengths must be an int64 tensor or None')
+            if tuple(lengths.shape) != (query.shape[0],):
+                raise ValueError('lengths must have shape [%d], got %s' % (query.shape[0], tuple(lengths.shape)))
+        _check_rnn_call(self, [t for t in (query, memory, keys, lengths) if t is not None])
+        if _lib.on_other_device(query):
+            with torch.cuda.device(query.device):
+                return self.forward(query, memory, lengths, keys)
+        from . import _infer_attn                                        # libqd_infer_attn.so: on first use only
+        lib = _infer_attn.load()
+        batch, S = memory.shape[0], memory.shape[1]
+        x = query.detach().contiguous()
+        q = x if self.linear_in is None else self.linear_in(x)
+        values = memory.detach().contiguous()
+        ks = values if keys is None else keys.detach().contiguous()
+        lens = None if lengths is None else lengths.contiguous()
+        align = torch.empty(batch, S, dtype=torch.float32, device=x.device)
+        ctx = torch.empty(batch, self.dim, dtype=torch.float32, device=x.device)
+        attn_h = torch.empty(batch, self.dim, dtype=torch.float32, device=x.device)
+        _infer_attn.check(lib.qda_attn_context_f32(q.data_ptr(), ks.data_ptr(), values.data_ptr(), None if lens is None else lens.data_ptr(),
+                                                   batch, S, self.dim, align.data_ptr(), ctx.data_ptr(), _lib.stream_ptr()))
+        o = self.out
+        _infer_attn.check(lib.qda_attn_out_packed_f32(o.packed.data_ptr(), o.alpha.data_ptr(), o.beta.data_ptr(), o.bucket_size or 0, o.s, o.bits,
+                                                      self.dim, ctx.data_ptr(), x.data_ptr(), batch, None if o.bias is None else o.bias.data_ptr(),
+                                                      attn_h.data_ptr(), None, _lib.stream_ptr()))
+        return attn_h, align
+
+    def unpack(self):
+        """(linear_out, linear_in or None): ordinary nn.Linear modules holding the fake-quantized fp32 weights (and the bias)."""
+        w = self.out._weight()
+        lin = nn.Linear(2 * self.dim, self.dim, bias=self.out.bias is not None, device=w.device)
+        with torch.no_grad():
+            lin.weight.copy_(w)
+            if self.out.bias is not None:
+                lin.bias.copy_(self.out.bias)
+        return lin, None if self.linear_in is None else self.linear_in.unpack()
 
 
 def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=None, conv=False, rnn=False):
