@@ -189,8 +189,13 @@ INFER_LIBRARIES = [
     # from the packed weight on fp32 MFMA.  INFER_MM_FLAGS for the reason of the rows above: the header words every fp32 operation
     # of both kernels as one scalar operation.
     ('libqd_infer_attn.so', ['qda_attn.hip'], 'qd_infer_attn.h', INFER_MM_FLAGS, '_infer_attn'),
+    # The end of a decoder step: the vocabulary projection on fp32 MFMA, reduced in registers to (max, sum of exp, top-k) per panel,
+    # and the launch that combines the panels.  INFER_MM_FLAGS: the logit is to have qdm_linear_packed_f32's bits (the bias one scalar
+    # v_add_f32), and the header words every fp32 operation of the reductions as one scalar operation.
+    ('libqd_infer_gen.so', ['qdn_generator.hip'], 'qd_infer_gen.h', INFER_MM_FLAGS, '_infer_gen'),
 ]
-INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES, INFER_GRU_SOURCES, INFER_ATTN_SOURCES = (row[1] for row in INFER_LIBRARIES)
+(INFER_SOURCES, INFER_MM_SOURCES, INFER_CONV_SOURCES, INFER_RNN_SOURCES, INFER_GRU_SOURCES, INFER_ATTN_SOURCES,
+ INFER_GEN_SOURCES) = (row[1] for row in INFER_LIBRARIES)
 
 
 def build_infer_library(library, force=False, verbose=False):
@@ -237,6 +242,10 @@ def build_infer_gru(force=False, verbose=False):
 
 def build_infer_attn(force=False, verbose=False):
     return build_infer_library('libqd_infer_attn.so', force, verbose)
+
+
+def build_infer_gen(force=False, verbose=False):
+    return build_infer_library('libqd_infer_gen.so', force, verbose)
 
 
 if __name__ == '__main__':

@@ -1,7 +1,8 @@
 """nn.Linear, nn.Embedding, nn.Conv2d, nn.LSTMCell, nn.LSTM, nn.GRUCell, nn.GRU and a Luong global-attention step that run straight from the packed level indices
 of a quantized weight (libqd_infer.so, include/qd_infer.h; for many rows of x libqd_infer_mm.so, include/qd_infer_mm.h;
 convolutions libqd_infer_conv.so, include/qd_infer_conv.h; LSTM steps libqd_infer_rnn.so, include/qd_infer_rnn.h; GRU steps
-libqd_infer_gru.so, include/qd_infer_gru.h; a global-attention step libqd_infer_attn.so, include/qd_infer_attn.h): a layer keeps `bits` bits per
+libqd_infer_gru.so, include/qd_infer_gru.h; a global-attention step libqd_infer_attn.so, include/qd_infer_attn.h; the generator with its
+log-softmax and top-k libqd_infer_gen.so, include/qd_infer_gen.h): a layer keeps `bits` bits per
 weight + (alpha, beta) per bucket on the device and never holds the fp32 tensor.  The format is codec.pack_uniform's for the
 2-D weight; the value of a weight is bit for bit what PackedUniform.unpack() gives.
 
@@ -873,6 +874,75 @@ class PackedGlobalAttention(nn.Module):
             if self.out.bias is not None:
                 lin.bias.copy_(self.out.bias)
         return lin, None if self.linear_in is None else self.linear_in.unpack()
+
+
+GeneratorOutput = collections.namedtuple('GeneratorOutput', 'log_probs lse top_values top_indices')
+
+
+class PackedGenerator(_PackedModule):
+    """The end of a decoder step -- generator = nn.Linear(dim, V), log_softmax and, in beam search, topk -- with W[V, dim] read
+    from its packed level indices (qdn_generator_packed_f32, libqd_infer_gen.so, include/qd_infer_gen.h, loaded on first use: two
+    launches, the logits reduced to (max, sum of exp, top-k) per panel of 64 words in the registers that hold them).
+
+    forward(x [..., dim], topk=0, log_probs=True) -> GeneratorOutput(log_probs [..., V] or None, lse [...], top_values [..., topk]
+    or None, top_indices [..., topk] int64 or None).  The logits have the bits of PackedLinear(batched_from=1) on the same weight;
+    log_probs = logits - lse; the top k are ordered as torch.topk orders them (NaN first, ties to the lower index) and hold -inf
+    and -1 from V on.  0 <= topk <= 16.  With log_probs=False the [m, V] array is never written.
+
+    pack_modules does not build this layer -- a generator is an nn.Linear like any other.  From the PackedLinear it leaves behind:
+    PackedGenerator(m.generator.as_packed_uniform(), bias=m.generator.bias)."""
+
+    @classmethod
+    def from_linear(cls, linear, s, bucket_size=256, bits=None):
+        """Quantize the weight of the generator's nn.Linear with `s` levels per bucket; bits=None takes codec.min_bits_for_levels(s)."""
+        if not isinstance(linear, nn.Linear):
+            raise TypeError('from_linear takes an nn.Linear, got %r' % type(linear))
+        pk = _pack_weight(linear.weight, s, bucket_size, bits, 'PackedGenerator.from_linear')
+        return cls(pk, None if linear.bias is None else linear.bias.detach().clone())
+
+    def forward(self, x, topk=0, log_probs=True):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError('x must be a torch.Tensor, got %r' % type(x))
+        if x.dtype != torch.float32:
+            raise TypeError('x must be float32, got %s' % x.dtype)
+        if x.dim() < 1 or x.shape[-1] != self.cols:
+            raise ValueError('x must have a last dimension of %d, got shape %s' % (self.cols, tuple(x.shape)))
+        if not isinstance(topk, int) or isinstance(topk, bool) or not 0 <= topk <= 16:
+            raise ValueError('topk must be an integer from 0 to 16, got %r' % (topk,))
+        _require_device(self.packed, 'PackedGenerator')
+        _require_device(x, 'PackedGenerator')
+        if x.device != self.packed.device:
+            raise ValueError('x lives on %s, the packed weight on %s' % (x.device, self.packed.device))
+        if x.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError('PackedGenerator is inference only and does not differentiate through x; run under torch.no_grad(), '
+                               'or train with unpack(), the nn.Linear of the fake-quantized weights')
+        if _lib.on_other_device(x):
+            with torch.cuda.device(x.device):
+                return self.forward(x, topk, log_probs)
+        from . import _infer_gen                                         # libqd_infer_gen.so: on first use only
+        lib = _infer_gen.load()
+        xc = x.detach().contiguous()
+        lead = tuple(x.shape[:-1])
+        m = int(torch.Size(lead).numel())
+        new = lambda shape, dtype=torch.float32: torch.empty(lead + shape, dtype=dtype, device=x.device)      # noqa: E731
+        lse = new(())
+        logp = new((self.rows,)) if log_probs else None
+        top_val, top_idx = (new((topk,)), new((topk,), torch.int64)) if topk else (None, None)
+        work = torch.empty(max(lib.qdn_generator_work_bytes(self.rows, m, topk), 4) // 4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: None if t is None else t.data_ptr()              # noqa: E731
+        _infer_gen.check(lib.qdn_generator_packed_f32(*self._format_args(), xc.data_ptr(), m, ptr(self.bias), lse.data_ptr(), ptr(logp), topk,
+                                                      ptr(top_val), ptr(top_idx), work.data_ptr(), _lib.stream_ptr()))
+        return GeneratorOutput(logp, lse, top_val, top_idx)
+
+    def unpack(self):
+        """An ordinary nn.Linear holding the fake-quantized fp32 weights (and the bias): the generator in front of log_softmax."""
+        w = self._weight()
+        lin = nn.Linear(self.cols, self.rows, bias=self.bias is not None, device=w.device)
+        with torch.no_grad():
+            lin.weight.copy_(w)
+            if self.bias is not None:
+                lin.bias.copy_(self.bias)
+        return lin
 
 
 def pack_modules(model, s, bucket_size=256, bits=None, skip=(), batched_from=None, conv=False, rnn=False):
