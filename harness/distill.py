@@ -425,6 +425,24 @@ def seq2seq_kd_loss_fn(student, teacher, src, tgt, side=None):
     return models.word_kd_loss(logits, t_logits(), tgt_out.flatten(), src.size(1))
 
 
+def fused_cnn_kd_loss_fn(student, teacher, images, labels, side=None):
+    """cnn_kd_loss_fn with the loss and its logit gradient from one call of libqd_loss.so (quantized_distillation_amd.kd_loss);
+    for DistillTrainer(loss_fn=...)."""
+    from quantized_distillation_amd import kd_loss
+    t_out = _teacher_forward(teacher, side, images)
+    out = student(images)
+    return kd_loss.fused_kd_loss(out, t_out(), labels)
+
+
+def fused_seq2seq_kd_loss_fn(student, teacher, src, tgt, side=None):
+    """seq2seq_kd_loss_fn with the loss and its logit gradient from one call of libqd_loss.so; for DistillTrainer(loss_fn=...)."""
+    from quantized_distillation_amd import kd_loss
+    tgt_in, tgt_out = tgt[:-1], tgt[1:]
+    t_logits = _teacher_forward(teacher, side, src, tgt_in)
+    logits = student(src, tgt_in)
+    return kd_loss.fused_word_kd_loss(logits, t_logits(), tgt_out.flatten(), src.size(1))
+
+
 def synthetic_token_batch(batch, device, seed=0, v_src=18000, v_tgt=10000, max_len=50):
     """multi30k-shaped synthetic batch: sequence-first int64 (len <= 50, batch), pad id 1."""
     g = torch.Generator().manual_seed(seed)

@@ -248,9 +248,32 @@ def build_infer_gen(force=False, verbose=False):
     return build_infer_library('libqd_infer_gen.so', force, verbose)
 
 
+LOSS_SOURCES = ['qdl_kd.hip']
+
+
+def build_loss(force=False, verbose=False):
+    """libqd_loss.so (include/qd_loss.h): the fused distillation loss, one hipcc call from csrc/loss/ with HIPCC_FLAGS.  No row of
+    INFER_LIBRARIES -- it is no inference library -- but their rule: stale against its sources, every header under csrc/, its
+    public header and this file; an atomic replace of a complete file at the path its binding module loads."""
+    from . import _loss
+    srcs = [os.path.join(_loss.CSRC, f) for f in LOSS_SOURCES]
+    deps = srcs + _headers() + [os.path.join(_lib.INCLUDE, 'qd_loss.h')]
+    out = _loss.LIB_PATH
+    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in deps):
+        return out
+    tmp = _tmp(out)
+    cmd = [hipcc()] + HIPCC_FLAGS + ['-I', _lib.INCLUDE] + srcs + ['-o', tmp]
+    if verbose:
+        print(' '.join(cmd))
+    subprocess.check_call(cmd)
+    os.replace(tmp, out)
+    return out
+
+
 if __name__ == '__main__':
     print(build_extension(force=True, verbose=True))
     for row in INFER_LIBRARIES:
         print(build_infer_library(row[0], force=True, verbose=True))
+    print(build_loss(force=True, verbose=True))
     print(build_glue(force=True, verbose=True))
     print(build_host(force=True, verbose=True))
